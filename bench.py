@@ -16,9 +16,13 @@ gather inside the C-ABI (rt_comm_init / rt_render_gather, include/rtpt.h) and
 the timed step includes it.  torch.distributed (gloo, CPU) only carries the
 communicator id, the barriers and the max over ranks.
 
-Prints one JSON line on rank 0.  The CPU baseline (rank 0, N=1 only) is the
-scalar C oracle (oracle/liboracle.so, "port") on every core this process may
-use, on a bounded sample of the same frame: rows of the timed image at the
+Prints one JSON line on rank 0.  A plain run sets up, warms up, times the steps
+and prints that line; `--dump-outputs DIR` also writes the frame of the last
+timed step to DIR/frame.npy.  Everything that takes work of its own is behind
+`--full`: the frame sanity check (`frame_ok`), the placement proof of an N > 1
+run (`gather_check`) and the CPU baseline.  The CPU baseline (rank 0, N=1 only)
+is the scalar C oracle (oracle/liboracle.so, "port") on every core this process
+may use, on a bounded sample of the same frame: rows of the timed image at the
 timed spp, which are also compared bit for bit with the GPU's timed frame.
 """
 from __future__ import annotations
@@ -43,6 +47,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 # instruction (a 64-lane op issues over 2 cycles on the 32-wide SIMD)
 VALU_PEAK_WAVE_INSTR = 256 * 4 * 2.4e9 / 2
 BYTES_PER_PIXEL = 4 + 16       # seed read (u32) + rgba32F store, per launch
+DUMP_MAX_BYTES = 64 * 10**6    # --dump-outputs writes at most this much
 
 
 def parse(argv=None):
@@ -61,12 +66,22 @@ def parse(argv=None):
                     help="random triangles added to the room for --scene triangles")
     ap.add_argument("--batch-spp", type=int, default=0,
                     help="progressive mode: launches of this many spp into a running sum")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the frame "
+                         "sanity check, the N > 1 placement proof and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; "
+                         "a fixed, seeded sample of its rows where it exceeds 64 MB)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"],
+                    help="with --full: 'off' skips the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads (default: every CPU this process may use: its "
                          "affinity, capped by the cgroup CPU quota)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def visible_gpus() -> int:
@@ -142,6 +157,23 @@ def gather_check_rows(H: int, world: int):
     """Rows rank 0 re-renders locally after an N > 1 run: the first row of
     every rank's tile and the last row of the frame."""
     return sorted(set(range(min(world, H))) | {H - 1})
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: what the timed path handed its caller in the last timed
+    step, the (H, W, 4) float32 frame, as DIR/frame.npy.  A frame above
+    DUMP_MAX_BYTES is cut to a fixed sample of whole rows (drawn with seed 0
+    from the H rows, in ascending order), the same for every run of one size."""
+    import torch
+    H, W = frame.shape[:2]
+    budget = DUMP_MAX_BYTES - 4096  # room for the .npy header
+    keep = max(1, budget // (W * 16))
+    if keep < H:
+        rows = np.sort(np.random.default_rng(0).choice(H, size=keep, replace=False))
+        frame = frame[torch.from_numpy(rows).to(frame.device)][:, :budget // 16]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "frame.npy"),
+            np.ascontiguousarray(frame.cpu().numpy(), dtype=np.float32))
 
 
 def load_profile_json(name):
@@ -307,7 +339,6 @@ def main(argv=None, backend_factory=CudaBackend):
 
     for _ in range(args.warmup):
         step()
-    launch = renderer.last_launch()
     events = [(be.event(), be.event()) for _ in range(args.steps)]
     barrier()
     t0 = time.perf_counter()
@@ -315,6 +346,7 @@ def main(argv=None, backend_factory=CudaBackend):
         step(events[k])
     barrier()
     elapsed = time.perf_counter() - t0
+    launch = renderer.last_launch()  # after the steps: --warmup 0 has none before them
     # HIP events on the stream the kernel runs on, around every timed step: at
     # N = 1 a step is exactly one kernel launch (or the launches of one
     # progressive frame).  At N > 1 a step also holds the gather: the kernel
@@ -344,9 +376,14 @@ def main(argv=None, backend_factory=CudaBackend):
         kernel_ms_max, step_ms_max = kernel_ms, step_ms
 
     if rank == 0:
-        frame_ok = bool(torch.isfinite(frame).all().item()) and bool((frame[..., 3] == 1).all().item())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)
+        frame_ok = None
+        if args.full:
+            frame_ok = (bool(torch.isfinite(frame).all().item())
+                        and bool((frame[..., 3] == 1).all().item()))
         gather_check = None
-        if world > 1:
+        if world > 1 and args.full:
             # placement proof: rows of every rank's tile, re-rendered here by
             # one local rt_render each, must equal the gathered frame bit for bit
             host = frame.cpu().numpy()
@@ -437,7 +474,7 @@ def main(argv=None, backend_factory=CudaBackend):
             out["gather_ms_basis"] = ("step - render launch on each rank (HIP events), max over ranks"
                                       if gather_ms is not None else
                                       "not separable: progressive launches and the gather run in one call")
-        if world == 1 and args.cpu_baseline != "off":
+        if args.full and world == 1 and args.cpu_baseline != "off":
             # every CPU this process may run on at once: the affinity mask,
             # capped by the cgroup CPU quota (oversubscribing a 16-CPU quota
             # with 256 threads measured 13.2 instead of 22.3 Msamples/s)

@@ -137,10 +137,10 @@ def _worker(rank, world, port, argv, swap, result_path):
             f.write(buf.getvalue())
 
 
-def _run(world, tmp_path, swap=False, H=17):
+def _run(world, tmp_path, swap=False, H=17, extra=("--full",)):
     W, spp, steps = 24, 2, 2
     argv = ["--gpus", str(world), "--width", str(W), "--height", str(H), "--spp", str(spp),
-            "--steps", str(steps), "--warmup", "1", "--cpu-baseline", "off"]
+            "--steps", str(steps), "--warmup", "1", "--cpu-baseline", "off", *extra]
     out = str(tmp_path / "line.json")
     mp.spawn(_worker, args=(world, _free_port(), argv, swap, out), nprocs=world, join=True)
     lines = [ln for ln in open(out).read().splitlines() if ln.startswith("{")]
@@ -173,6 +173,46 @@ def test_bench_multirank_line(world, tmp_path):
 def test_bench_placement_proof_catches_misplaced_tiles(tmp_path):
     rec, *_ = _run(2, tmp_path, swap=True)
     assert rec["gather_check"]["bit_exact_vs_local_render"] is False
+
+
+def test_bench_plain_run_dumps_the_gathered_frame(tmp_path):
+    """Without --full the line keeps its headline keys and leaves the checks
+    out; --dump-outputs writes rank 0's gathered frame of the last timed step:
+    float32, every pixel, equal to the oracle's frame bit for bit, and the same
+    bytes from a second run with the same arguments."""
+    import oracle_lib
+    from gpuraytracer_amd import Scene, seed_splitmix
+    frames = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        rec, W, H, spp, steps = _run(2, tmp_path, extra=("--dump-outputs", str(d)))
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0 and rec["dtype"] == "f32"
+        assert rec["unit"] == "Msamples/s" and rec["higher_is_better"] is True
+        assert rec["frame_ok"] is None and rec["gather_check"] is None
+        assert rec["cpu_baseline"] is None
+        assert sorted(os.listdir(d)) == ["frame.npy"]
+        frames.append(np.load(d / "frame.npy"))
+    assert frames[0].dtype == np.float32 and frames[0].shape == (H, W, 4)
+    assert frames[0].tobytes() == frames[1].tobytes()
+    ref = oracle_lib.render(Scene.cornell_box(W, H), seed_splitmix(W, H), spp * 2, 3)
+    assert np.array_equal(frames[0].view(np.uint32), ref.view(np.uint32))
+
+
+def test_dump_outputs_samples_a_frame_over_the_size_limit(tmp_path, monkeypatch):
+    """A frame above the limit is cut to a fixed, seeded set of whole rows:
+    the same rows on every call, under the limit on disk."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 5 * 8 * 16 + 15)  # room for 5 rows of 8
+    frame = torch.arange(13 * 8 * 4, dtype=torch.float32).reshape(13, 8, 4)
+    bench.dump_outputs(str(tmp_path / "a"), frame)
+    bench.dump_outputs(str(tmp_path / "b"), frame)
+    a, b = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "b" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (5, 8, 4) and np.array_equal(a, b)
+    rows = (a[:, 0, 0] / 32).astype(int)
+    assert len(set(rows)) == 5 and list(rows) == sorted(rows)
+    assert np.array_equal(a, frame.numpy()[rows])
+    assert os.path.getsize(tmp_path / "a" / "frame.npy") <= bench.DUMP_MAX_BYTES
 
 
 def test_spawn_ranks_refuses_more_ranks_than_gpus():

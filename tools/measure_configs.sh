@@ -16,7 +16,7 @@ run() {  # run <name> <seconds> <cmd...>
   timeout -k 10 "$lim" "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "[configs] $name failed" >&2; tail "$OUT/$name.err" >&2; exit 1; }
   tail -c 300 "$OUT/$name.json" >&2; echo >&2
 }
-run c1_128sq_1spp 120 python bench.py --width 128 --height 128 --spp 1 --steps 5 --warmup 1
+run c1_128sq_1spp 120 python bench.py --width 128 --height 128 --spp 1 --steps 5 --warmup 1 --full
 run c2_1080p_256spp 180 python bench.py --steps 5 --warmup 1 --cpu-baseline off
 run c3_share_4096sq_128spp 180 python bench.py --width 4096 --height 4096 --spp 128 --steps 2 --warmup 1 --cpu-baseline off
 run c4_spheres1000 180 python bench.py --scene spheres --steps 3 --warmup 1 --cpu-baseline off
