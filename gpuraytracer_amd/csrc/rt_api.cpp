@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rtpt.h"
+#include "rt_beam.hpp"
 #include "rt_kernel.hpp"
 #include "rt_scene.hpp"
 
@@ -36,7 +37,6 @@ struct rt_ctx {
     float4* d_tri_shade = nullptr;
     float4* d_pair_isect = nullptr;
     float4* d_clusters = nullptr;
-    float4* d_clu_oct = nullptr;     // rt_scene.hpp clu_oct
     uint32_t* d_sph_lds = nullptr;
     uint16_t* d_sph_lds_id = nullptr;
     uint4* d_sph_box = nullptr;      // the leaf-box layout of the sphere BVH (rt_scene.hpp sph_box)
@@ -137,7 +137,6 @@ void release(rt_ctx* c) {
     (void)hipFree(c->d_tri_shade);
     (void)hipFree(c->d_pair_isect);
     (void)hipFree(c->d_clusters);
-    (void)hipFree(c->d_clu_oct);
     (void)hipFree(c->d_sph_lds);
     (void)hipFree(c->d_sph_lds_id);
     (void)hipFree(c->d_sph_box);
@@ -241,7 +240,6 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     K.tri_shade = c->d_tri_shade;
     K.pair_isect = c->d_pair_isect;
     K.clusters = c->d_clusters;
-    K.clu_oct = c->d_clu_oct;
     K.nC = (uint32_t)(c->scene.clusters.size() / (4 * rt::kCluF4));
     K.pair_free = c->scene.pair_free_mask;
     K.sph_isect = c->d_sph_isect;
@@ -734,7 +732,6 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
             (e = upload(&c->d_tri_shade, s.tri_shade.data(), s.tri_shade.size() * sizeof(rt::TriShade), c->stream)) != hipSuccess ||
             (e = upload(&c->d_pair_isect, s.pair_isect.data(), s.pair_isect.size() * sizeof(rt::PairIsect), c->stream)) != hipSuccess ||
             (e = upload(&c->d_clusters, s.clusters.data(), s.clusters.size() * sizeof(float), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_clu_oct, s.clu_oct.data(), s.clu_oct.size() * sizeof(float), c->stream)) != hipSuccess ||
             (e = upload(&c->d_sph_lds, s.sph_lds.data(), s.sph_lds.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
             (e = upload(&c->d_sph_lds_id, s.sph_lds_id.data(), s.sph_lds_id.size() * sizeof(uint16_t), c->stream)) != hipSuccess ||
             (e = upload(&c->d_sph_box, s.sph_box.data(), s.sph_box.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
@@ -1060,6 +1057,27 @@ int rt_scene_describe_ex(const rt_scene_desc* d, const rt_create_options* opt, r
                           info->n_triangle_bvh_nodes, !s.sph_lds.empty(), 3, ro.mem, ro.walk);
     info->kernel_layout = (uint32_t)kc.layout;
     info->kernel_lds_bytes = (uint32_t)kc.lds_bytes;
+    return RT_OK;
+}
+
+int rt_debug_camera_candidates(const rt_scene_desc* d, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                               uint8_t* may_hit) {
+    if (!d || !may_hit || !d->camera || !d->square_lights || x1 < x0 || y1 < y0 || x0 < 0 || y0 < 0)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "null argument or empty rectangle");
+    rt::CompiledScene s;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0],
+                           d->spheres, d->n_spheres, &s, &err))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    memset(may_hit, 1, d->n_triangles);
+    const rt::CamConst& c = s.cam;
+    // the kernel's own floats: (float) of the unsigned pixel coordinates, W and H
+    const rt::Beam beam = rt::make_beam(rt::f3{c.pos[0], c.pos[1], c.pos[2]}, rt::f3{c.u[0], c.u[1], c.u[2]},
+                                        rt::f3{c.v[0], c.v[1], c.v[2]}, rt::f3{c.w[0], c.w[1], c.w[2]}, c.halfW,
+                                        c.halfH, (float)c.W, (float)c.H, (float)(uint32_t)x0, (float)(uint32_t)x1,
+                                        (float)(uint32_t)y0, (float)(uint32_t)y1);
+    for (size_t k = 0; k < s.pair_isect.size(); ++k)
+        if (rt::beam_excludes_pair(beam, s.pair_isect[k].q)) may_hit[2 * k] = may_hit[2 * k + 1] = 0;
     return RT_OK;
 }
 

@@ -28,6 +28,7 @@
 
 #include "rt_kernel.hpp"
 #include "rt_halton.hpp"
+#include "rt_beam.hpp"
 #include "rt_trace.hpp"
 
 namespace rt {
@@ -633,7 +634,7 @@ void path_trace_kernel(KParams P) {
         constexpr bool pairs = GEO == kGeoPairLds || GEO == kGeoPairClu || GEO == kGeoSphLds;
         const uint32_t ng4 = pairs ? kPairF4 * sv.nP : 3u * sv.nT;
         const float4* src = pairs ? P.pair_isect : P.tri_isect;
-        RT_LDS_GUARD(16 * (size_t)(ng4 + (GEO == kGeoPairClu ? (kCluF4 + kCluOctF4) * P.nC : 0u)) +
+        RT_LDS_GUARD(16 * (size_t)(ng4 + (GEO == kGeoPairClu ? kCluF4 * P.nC : 0u)) +
                      (GEO == kGeoPairClu ? 4 * (size_t)kHaltonTabFloats : 0));
         for (uint32_t k = threadIdx.x; k < ng4; k += NT) lds[k] = src[k];
         if (GEO == kGeoSphLds) {  // the compact sphere BVH (8 layouts) stays in global memory (L2)
@@ -646,10 +647,7 @@ void path_trace_kernel(KParams P) {
         }
         if (GEO == kGeoPairClu) {  // box clusters after the pair records, then the Halton tables
             for (uint32_t k = threadIdx.x; k < kCluF4 * P.nC; k += NT) lds[ng4 + k] = P.clusters[k];
-            for (uint32_t k = threadIdx.x; k < kCluOctF4 * P.nC; k += NT)
-                lds[ng4 + kCluF4 * P.nC + k] = P.clu_oct[k];
-            sv.clu_oct = kCluOctF4 ? lds + ng4 + kCluF4 * P.nC : nullptr;
-            const uint32_t tab0 = ng4 + (kCluF4 + kCluOctF4) * P.nC;
+            const uint32_t tab0 = ng4 + kCluF4 * P.nC;
             const bool tab = halton_tables_on(GEO, SMALL, P.spp, L);
             sv.htab = tab ? reinterpret_cast<const float*>(lds + tab0) : nullptr;
             if (tab) fill_halton_tables(reinterpret_cast<float*>(lds + tab0), threadIdx.x, NT);
@@ -707,6 +705,27 @@ void path_trace_kernel(KParams P) {
         x = bx * (WR * kWX) + (wave % WR) * kWX + (pix % kWX);
         j = by * (WC * kWY) + (wave / WR) * kWY + (pix / kWX);
     };
+    if constexpr (RT_CAM_CAND && GEO == kGeoPairClu) {
+        // The pairs this wave's camera rays can hit (rt_beam.hpp, DESIGN.md
+        // §3.16), once per wave: the footprint is the wave's pixel rectangle
+        // from the tile geometry (the same for the whole launch), lane k tests
+        // pair k (nP <= 31 with box clusters) and the ballot is the mask.
+        // Before the early return below: a ballot only sees active lanes.
+        if (sv.nP - 1u < 32u) {  // wave-uniform: 1..32 pairs, else cluster_query as before
+            const uint32_t wave = wave_uniform(threadIdx.x >> 6);
+            const uint32_t wx0 = bx * (WR * kWX) + (wave % WR) * kWX;
+            const uint32_t wj0 = by * (WC * kWY) + (wave / WR) * kWY;
+            const float y0 = (float)(P.row_start + wj0 * P.row_step);
+            const float y1 = (float)(P.row_start + (wj0 + kWY - 1u) * P.row_step);
+            const Beam beam = make_beam(ld_f3(P.cam_pos), ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), P.halfW,
+                                        P.halfH, (float)P.W, (float)P.H, (float)wx0, (float)(wx0 + kWX - 1u), y0, y1);
+            const uint32_t k = threadIdx.x & 63u;
+            const uint32_t kc = min(k, sv.nP - 1u);  // lanes past the last pair re-test it (discarded)
+            const bool keep = !beam_excludes_pair(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * kc));
+            sv.cam_mask = wave_uniform((uint32_t)__builtin_amdgcn_ballot_w64(k < sv.nP && keep));
+            sv.cam_avail = true;
+        }
+    }
     // Per-lane constants (pixel coordinates, lane roles) are recomputed from an
     // opaque copy of threadIdx.x where they are used, and the seed is kept in
     // LDS: otherwise the compiler hoists them out of the sample loop and spills

@@ -155,10 +155,11 @@ struct SceneView {
     uint32_t nTN;
     uint32_t nT, nP, nS, nN;
     const float4* clu;        // box clusters, kCluF4 float4 each (kGeoPairClu)
-    const float4* clu_oct = nullptr;  // per cluster, 8 octants x 2 float4 of pre-swapped face masks, or null
     uint32_t nC;
     uint32_t pair_free;       // pairs in no cluster: tested by every lane
-    const float* htab;        // Halton low-digit tables in LDS (kGeoPairClu)
+    uint32_t cam_mask = 0;    // wave-uniform: pairs the wave's camera rays can hit (rt_beam.hpp), free pairs included
+    bool cam_avail = false;   // cam_mask was computed (a mask of 0 is a valid answer)
+    const float* htab;       // Halton low-digit tables in LDS (kGeoPairClu)
     const uint4* sent;        // compact sphere BVH entries (kGeoSphLds): 8 octant layouts, global
     const uint16_t* sid;      // sphere id of each compact entry (leaves), global
     const uint4* sbox;        // the sphere BVH with leaf boxes (RT_SPH_LEAFBOX): 8 layouts of nSB entries
@@ -842,17 +843,11 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
     const float oi[3] = {rb.oinv.x, rb.oinv.y, rb.oinv.z};
     uint32_t mask = 0;
     uint32_t c = 0;
-    // the face masks: the cluster record's, or with the octant table the row of
-    // this ray's octant, where world axes need no select (rt_scene.cpp clu_oct)
-    const bool oct = RT_CLU_OCT && sv.clu_oct != nullptr;  // wave-uniform
-    const uint32_t octant = (iv[0] < 0.0f ? 1u : 0u) | (iv[1] < 0.0f ? 2u : 0u) | (iv[2] < 0.0f ? 4u : 0u);
-    const float4* mrow = oct ? sv.clu_oct + 2u * octant : sv.clu + 4;
-    const uint32_t mstride = oct ? kCluOctF4 : kCluF4;
     for (; c < sv.nC; ++c) {
         if (SEG && ((skip >> c) & 1u)) continue;
         const float4* r = sv.clu + kCluF4 * c;
         const float4 H = r[3], W = r[6];
-        const float4 M0 = mrow[mstride * c], M1 = mrow[mstride * c + 1];
+        const float4 M0 = r[4], M1 = r[5];
         const uint32_t flags = __float_as_uint(H.w);
         if (flags & 16u) break;  // single-face clusters come last (rt_scene.cpp)
         const float hi[3] = {H.x, H.y, H.z}, wf[3] = {W.x, W.y, W.z};
@@ -886,12 +881,9 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
             // a ray with d_a >= 0 enters through the low face (slot 2a) and
             // leaves through the high one (2a + 1); the face plane lies
             // wf * |1/d_a| inside the padded slab, +- the tolerance
-            uint32_t m_en = m[2 * a], m_ex = m[2 * a + 1];
-            if (!(RT_CLU_OCT && oct && (flags & (1u << a)))) {  // wave-uniform
-                const bool neg = ida[a] < 0.0f;
-                m_en = neg ? m[2 * a + 1] : m[2 * a];
-                m_ex = neg ? m[2 * a] : m[2 * a + 1];
-            }
+            const bool neg = ida[a] < 0.0f;
+            const uint32_t m_en = neg ? m[2 * a + 1] : m[2 * a];
+            const uint32_t m_ex = neg ? m[2 * a] : m[2 * a + 1];
             const float wa = wf[a] * fabsf(ida[a]);
             cm |= (en[a] + fmaf(fabsf(en[a]), kEps, wa) >= tlo) ? m_en : 0u;
             cm |= (ex[a] - fmaf(fabsf(ex[a]), kEps, wa) <= thi) ? m_ex : 0u;
@@ -1099,7 +1091,19 @@ __device__ __forceinline__ int closest_hit(const SceneView& sv, f3& o, f3& d, fl
     float best = *t_io;
     int id = -1;
     if (GEO == kGeoPairClu) {
-        cluster_query<false>(sv, o, d, tmin, &best, &id);
+        if (RT_CAM_CAND && CULL && sv.cam_avail) {
+            // camera rays: the wave's candidate pairs, the same for every lane
+            // and sample (scalar k: same-address LDS reads); (t, id) ranking
+            // makes the visiting order free
+            for (uint32_t m = sv.cam_mask; m != 0u; m &= m - 1u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(m);
+                RT_STAT(13, 1);
+                RT_STAT(14, __popcll(__ballot(1)));
+                pair_test_rank<false>(sv.pair + kPairF4 * k, k, o, d, tmin, &best, &id);
+            }
+        } else {
+            cluster_query<false>(sv, o, d, tmin, &best, &id);
+        }
     } else if (geo_pairs(GEO)) {
         f3 seg_lo, seg_hi;
         if (CULL) {

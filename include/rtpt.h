@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RTPT_ABI_VERSION 7
+#define RTPT_ABI_VERSION 8
 
 /* Maximum bounce count: Halton dimensions 2+5b..5+5b must stay inside the
  * 24-entry `primes[]` table (`RTrace/sampling.metal:97-104`); b <= 3. */
@@ -379,6 +379,18 @@ typedef struct rt_scene_info {
 } rt_scene_info;
 int rt_scene_describe(const rt_scene_desc* scene, rt_scene_info* info);
 int rt_scene_describe_ex(const rt_scene_desc* scene, const rt_create_options* opt, rt_scene_info* info);
+
+/* Debug (host-only, no context, no device): which triangles the camera rays of
+ * the pixel rectangle [x0, x1] x [y0, y1] (closed, any jitter in [0, 1]) can
+ * hit, by the test the box-cluster kernel runs once per wave for its bounce-0
+ * closest query (gpuraytracer_amd/csrc/rt_beam.hpp).
+ * may_hit: one byte per triangle id, 1 = the triangle's pair stays a
+ * candidate.  The test runs on every scene that has pair records (every
+ * (2k, 2k+1) shares v0 and an edge), whether or not a render of it takes the
+ * box-cluster kernel (which needs box clusters and at most 31 pairs); a scene
+ * without pair records gets all ones. */
+int rt_debug_camera_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                               uint8_t* may_hit);
 
 /* The reference's image epilogue (RTrace/image.swift:35-65): fp16 round trip,
  * ×2 exposure, Reinhard, gamma 1/2.2, clamp, truncating UInt8, alpha 255.
