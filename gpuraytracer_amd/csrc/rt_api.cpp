@@ -243,9 +243,12 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     K.nC = (uint32_t)(c->scene.clusters.size() / (4 * rt::kCluF4));
     K.pair_free = c->scene.pair_free_mask;
     K.sph_isect = c->d_sph_isect;
-    K.sph_lds = c->scene.sph_lds.empty() ? nullptr : c->d_sph_lds;
+    // both compact tables or neither: the launcher takes the sphere kernel when
+    // sph_lds is set, and that kernel's walks read sph_box (rt_scene.hpp)
+    const bool sph_compact = rt::sphere_compact_usable(c->scene);
+    K.sph_lds = sph_compact ? c->d_sph_lds : nullptr;
     K.sph_lds_id = c->d_sph_lds_id;
-    K.sph_box = c->scene.sph_box.empty() ? nullptr : c->d_sph_box;
+    K.sph_box = (sph_compact && !c->scene.sph_box.empty()) ? c->d_sph_box : nullptr;
     K.sph_shade = c->d_sph_shade;
     K.sph_nodes = c->d_sph_nodes;
     K.sph_perm = c->d_sph_perm;
@@ -1041,7 +1044,7 @@ int rt_scene_describe_ex(const rt_scene_desc* d, const rt_create_options* opt, r
     info->n_triangle_bvh_nodes = bvh ? 2 * info->n_triangles - 1 : 0u;
     // the launcher takes the sphere kernel only for the pair layout (every
     // triangle paired) and no triangle BVH, with its pair copy within 6 KB
-    info->sphere_kernel_lds_bytes = (!s.sph_lds.empty() && info->n_triangle_pairs > 0 && !bvh &&
+    info->sphere_kernel_lds_bytes = (rt::sphere_compact_usable(s) && info->n_triangle_pairs > 0 && !bvh &&
                                      ro.mem == rt::SceneMem::kAuto && lds <= rt::kSphPairLdsMaxBytes)
                                         ? (uint32_t)lds
                                         : 0u;
@@ -1054,7 +1057,7 @@ int rt_scene_describe_ex(const rt_scene_desc* d, const rt_create_options* opt, r
     // the launcher's own choice (rt::choose_kernel), for a render of >= 1 bounce
     const rt::KernelChoice kc =
         rt::choose_kernel(info->n_triangles, info->n_triangle_pairs, info->n_spheres, info->n_box_clusters,
-                          info->n_triangle_bvh_nodes, !s.sph_lds.empty(), 3, ro.mem, ro.walk);
+                          info->n_triangle_bvh_nodes, rt::sphere_compact_usable(s), 3, ro.mem, ro.walk);
     info->kernel_layout = (uint32_t)kc.layout;
     info->kernel_lds_bytes = (uint32_t)kc.lds_bytes;
     return RT_OK;

@@ -122,7 +122,9 @@ __host__ __device__ constexpr size_t staged_lds_bytes(int lay, uint32_t nT, uint
 }
 // The kernel layout a launch takes and its dynamic LDS (launch_path_trace and
 // rt_scene_describe_ex both ask this one function).  nC: box clusters, nTN:
-// triangle-BVH nodes per layout, sph_compact: the compact sphere BVH exists.
+// triangle-BVH nodes per layout, sph_compact: every table of the compact
+// sphere kernel exists (rt_scene.hpp sphere_compact_usable; the launcher reads
+// it from P.sph_lds, which rt_api.cpp sets by that predicate).
 struct KernelChoice {
     int layout;
     size_t lds_bytes;

@@ -267,10 +267,11 @@ class Scene:
         return cls(base.camera, mats, verts, base.light)
 
     def describe(self, options: Options | None = None) -> dict:
-        """Device layout rt_create would choose (rt_scene_describe_ex).  It
-        describes the lockstep kernels: with ``walk`` free or sorted a BVH
-        scene runs another kernel (``Renderer.last_launch()`` names it and its
-        LDS bytes)."""
+        """Device layout rt_create would choose (rt_scene_describe_ex).
+        ``kernel_layout`` and ``kernel_lds_bytes`` follow ``options.walk``
+        (layouts 8-11 for free and sorted on a BVH scene): the launcher's own
+        choice, the kernel ``Renderer.last_launch()`` names after a render of
+        >= 1 bounce.  Only ``n_triangle_bvh_nodes`` is an estimate."""
         info = SceneInfo()
         opt = None if options is None else ctypes.byref(options.c())
         _check(lib.rt_scene_describe_ex(ctypes.byref(self.desc()), opt, ctypes.byref(info)))

@@ -355,8 +355,13 @@ int rt_scene_cornell_box_mis(int32_t width, int32_t height, CameraGPU* camera,
 
 /* How rt_create would lay a scene out on the device (host-only, no device),
  * with default options; rt_scene_describe_ex with `opt` (NULL = defaults).
- * It describes the lockstep kernels: with walk_scheduler FREE or SORTED a BVH
- * scene runs another kernel, whose name and LDS bytes rt_last_launch reports. */
+ * kernel_layout and kernel_lds_bytes follow opt->walk_scheduler (layouts 8-11
+ * for FREE and SORTED on a BVH scene) and are the launcher's own choice: the
+ * kernel rt_last_launch names after a render of >= 1 bounce with these options.
+ * Only n_triangle_bvh_nodes is an estimate (see below).  A sphere scene whose
+ * tree has a leaf of more than 128 spheres (sphere_leaf_max > 128) or a
+ * non-finite node box takes layout 1, the pair kernel with the 32-B-node walk,
+ * and reports sphere_kernel_lds_bytes == 0. */
 typedef struct rt_scene_info {
     uint32_t n_triangles;
     uint32_t n_triangle_pairs;   /* >0: every (2k,2k+1) shares v0 and an edge -> pair records */
