@@ -21,6 +21,7 @@
 
 #include "../../include/rtpt.h"
 #include "rt_beam.hpp"
+#include "rt_shaft.hpp"
 #include "rt_kernel.hpp"
 #include "rt_scene.hpp"
 
@@ -1081,6 +1082,47 @@ int rt_debug_camera_candidates(const rt_scene_desc* d, int32_t x0, int32_t x1, i
                                         (float)(uint32_t)y0, (float)(uint32_t)y1);
     for (size_t k = 0; k < s.pair_isect.size(); ++k)
         if (rt::beam_excludes_pair(beam, s.pair_isect[k].q)) may_hit[2 * k] = may_hit[2 * k + 1] = 0;
+    return RT_OK;
+}
+
+int rt_debug_shadow_candidates(const rt_scene_desc* d, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                               uint8_t* may_occlude, int32_t* available) {
+    if (!d || !may_occlude || !available || !d->camera || !d->square_lights || x1 < x0 || y1 < y0 || x0 < 0 ||
+        y0 < 0)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "null argument or empty rectangle");
+    rt::CompiledScene s;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0],
+                           d->spheres, d->n_spheres, &s, &err))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    memset(may_occlude, 1, d->n_triangles);
+    *available = 0;
+    const size_t nP = s.pair_isect.size();
+    if (nP == 0) return RT_OK;
+    const rt::CamConst& c = s.cam;
+    const rt::Beam beam = rt::make_beam(rt::f3{c.pos[0], c.pos[1], c.pos[2]}, rt::f3{c.u[0], c.u[1], c.u[2]},
+                                        rt::f3{c.v[0], c.v[1], c.v[2]}, rt::f3{c.w[0], c.w[1], c.w[2]}, c.halfW,
+                                        c.halfH, (float)c.W, (float)c.H, (float)(uint32_t)x0, (float)(uint32_t)x1,
+                                        (float)(uint32_t)y0, (float)(uint32_t)y1);
+    const rt::ShaftLight L = rt::shaft_light(rt::f3{s.light.center[0], s.light.center[1], s.light.center[2]});
+    // the kernel's prologue: the union over the source triangles of the
+    // wave's camera mask; a light's triangle ends the path (no shadow ray)
+    std::vector<uint8_t> keep(nP, 0);
+    bool ok = true;
+    for (size_t k = 0; k < nP; ++k) {
+        if (rt::beam_excludes_pair(beam, s.pair_isect[k].q)) continue;
+        for (int tb = 0; tb < 2; ++tb) {
+            const float* sh = s.tri_shade[2 * k + tb].s;
+            if (sh[3] != 0.0f) continue;
+            const rt::ShaftSrc S = rt::shaft_source(beam, s.pair_isect[k].q, tb, rt::f3{sh[0], sh[1], sh[2]}, L);
+            ok = ok && S.ok;
+            for (size_t j = 0; j < nP; ++j)
+                if (!rt::shaft_excludes_pair(S, L, s.pair_isect[j].q)) keep[j] = 1;
+        }
+    }
+    if (!ok) return RT_OK;
+    *available = 1;
+    for (size_t j = 0; j < nP; ++j) may_occlude[2 * j] = may_occlude[2 * j + 1] = keep[j];
     return RT_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "rt_kernel.hpp"
 #include "rt_halton.hpp"
 #include "rt_beam.hpp"
+#include "rt_shaft.hpp"
 #include "rt_trace.hpp"
 
 namespace rt {
@@ -724,6 +725,39 @@ void path_trace_kernel(KParams P) {
             const bool keep = !beam_excludes_pair(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * kc));
             sv.cam_mask = wave_uniform((uint32_t)__builtin_amdgcn_ballot_w64(k < sv.nP && keep));
             sv.cam_avail = true;
+            if constexpr (RT_SHD_CAND) {
+                // The pairs that can occlude this wave's bounce-0 shadow rays
+                // (rt_shaft.hpp), for a wave whose camera
+                // mask holds ONE pair (nine tiles in ten; the beam is then dead
+                // before the target tests: no spill): lane k and lane k + 32
+                // test target pair k against the shafts of its triangle A and
+                // its triangle B; the mask is the union.  A light's triangle
+                // ends the path: it casts no shadow ray.  More source pairs:
+                // nothing is decided, the generic query runs.
+                const uint32_t tb = k >> 5, kt = min(k & 31u, sv.nP - 1u);
+                bool occ = false, bad = (sv.cam_mask & (sv.cam_mask - 1u)) != 0u;
+                if (sv.cam_mask != 0u && !bad) {  // wave-uniform
+                    const uint32_t sp = (uint32_t)__builtin_ctz(sv.cam_mask);
+                    const float4 s0 = P.tri_shade[4 * (2u * sp + tb)];
+                    if (s0.w == 0.0f) {
+                        const ShaftLight lq = shaft_light(ld_f3(P.light_center));
+                        const ShaftSrc src = shaft_source(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * sp),
+                                                          (int)tb, f3{s0.x, s0.y, s0.z}, lq);
+                        bad = !src.ok;
+                        occ = !shaft_excludes_pair(src, lq, reinterpret_cast<const float*>(sv.pair + kPairF4 * kt));
+                    }
+                }
+                const unsigned long long ob = __builtin_amdgcn_ballot_w64((k & 31u) < sv.nP && occ);
+                sv.shd_mask = wave_uniform((uint32_t)ob | (uint32_t)(ob >> 32));
+                sv.shd_avail = __builtin_amdgcn_ballot_w64(bad) == 0ull && sv.nC <= 32u;
+                // clusters none of whose faces is in the mask (record word 22: all its pairs)
+                if (sv.nC != 0u) {
+                    const uint32_t kc2 = min(k, sv.nC - 1u);
+                    const uint32_t all = __float_as_uint(reinterpret_cast<const float*>(sv.clu + kCluF4 * kc2)[22]);
+                    sv.shd_cskip = wave_uniform(
+                        (uint32_t)__builtin_amdgcn_ballot_w64(k < sv.nC && (all & sv.shd_mask) == 0u));
+                }
+            }
         }
     }
     // Per-lane constants (pixel coordinates, lane roles) are recomputed from an

@@ -36,6 +36,13 @@ constexpr uint32_t kCluF4 = 7;   // float4 per box cluster (rt_scene.hpp Compile
 #ifndef RT_CAM_CAND
 #define RT_CAM_CAND 1
 #endif
+// Its bounce-0 shadow query tests only the pairs that can occlude a segment
+// from the wave's camera-ray hit points to the light patch: one occluder mask
+// per wave from the same prologue (rt_shaft.hpp; needs
+// RT_CAM_CAND); 0: cluster_query as for every other shadow ray
+#ifndef RT_SHD_CAND
+#define RT_SHD_CAND 1
+#endif
 // Layouts of the triangle BVH (rt_scene.cpp build_tri_sah / rt_lbvh.hip,
 // rt_trace.hpp tri_cbvh_*): one per direction octant, 16 B per node.
 constexpr uint32_t kTriCompactLayouts = 8;

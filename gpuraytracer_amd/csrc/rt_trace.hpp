@@ -159,6 +159,9 @@ struct SceneView {
     uint32_t pair_free;       // pairs in no cluster: tested by every lane
     uint32_t cam_mask = 0;    // wave-uniform: pairs the wave's camera rays can hit (rt_beam.hpp), free pairs included
     bool cam_avail = false;   // cam_mask was computed (a mask of 0 is a valid answer)
+    uint32_t shd_mask = 0;    // wave-uniform: pairs that can occlude the wave's bounce-0 shadow rays (rt_shaft.hpp)
+    uint32_t shd_cskip = 0;   // wave-uniform: box clusters none of whose faces is in shd_mask
+    bool shd_avail = false;   // shd_mask was computed (a mask of 0: no shadow ray is occluded)
     const float* htab;       // Halton low-digit tables in LDS (kGeoPairClu)
     const uint4* sent;        // compact sphere BVH entries (kGeoSphLds): 8 octant layouts, global
     const uint16_t* sid;      // sphere id of each compact entry (leaves), global
@@ -816,9 +819,12 @@ __device__ __forceinline__ void tri_cbvh_walk(const uint4* __restrict__ cn, cons
 // normal tolerance from each face plane: the box is convex, so the segment
 // stays away from every face and no face can accept a hit.  The shrunk box
 // is precomputed on the host into the container's unused axis slots.
-template <bool SEG = false>
+// ALLOW (the bounce-0 shadow query): clusters in the wave-uniform set cskip
+// hold no pair of the wave's occluder mask and are skipped before their slab
+// terms are formed, the container check with them.
+template <bool SEG = false, bool ALLOW = false>
 __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o, f3 d, float tmin,
-                                                       float tmax) {
+                                                       float tmax, uint32_t cskip = 0u) {
     constexpr float kEps = 1.52587890625e-05f;  // 2^-16 relative slack
     // containers the whole wave's segments stay inside (wave-uniform bit mask),
     // decided before the slab terms are live
@@ -826,6 +832,7 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
     if (SEG) {
         const f3 e = o + d * tmax;
         for (uint32_t c = 0; c < sv.nC; ++c) {
+            if (ALLOW && ((cskip >> c) & 1u)) continue;
             const float4* r = sv.clu + kCluF4 * c;
             if (!(__float_as_uint(r[3].w) & 8u)) continue;
             // the shrunk box (rt_scene.cpp): face plane + tol_seg, with a 2^-20
@@ -844,8 +851,12 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
     uint32_t mask = 0;
     uint32_t c = 0;
     for (; c < sv.nC; ++c) {
-        if (SEG && ((skip >> c) & 1u)) continue;
         const float4* r = sv.clu + kCluF4 * c;
+        if (ALLOW && ((cskip >> c) & 1u)) {
+            if (__float_as_uint(r[3].w) & 16u) break;  // single-face clusters come last
+            continue;
+        }
+        if (SEG && ((skip >> c) & 1u)) continue;
         const float4 H = r[3], W = r[6];
         const float4 M0 = r[4], M1 = r[5];
         const uint32_t flags = __float_as_uint(H.w);
@@ -893,6 +904,7 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
     // single-face clusters (the light, lone rectangles): the face is a
     // candidate whenever the padded box is hit (a superset of its face test)
     for (; c < sv.nC; ++c) {
+        if (ALLOW && ((cskip >> c) & 1u)) continue;
         const float4* r = sv.clu + kCluF4 * c;
         const float4 A0 = r[0], A1 = r[1], A2 = r[2], H = r[3];
         const uint32_t flags = __float_as_uint(H.w);
@@ -997,14 +1009,17 @@ __device__ __forceinline__ uint32_t select_bit64(uint64_t m, uint32_t r) {
 // tmax and is not changed.
 // SEG: skip containers the wave's segments [o, o + d*tmax] stay inside (any
 // hit, and the MIS light queries: closest hits that only matter up to tmax).
-template <bool ANY, bool SEG = ANY>
+// ALLOW (the bounce-0 shadow query): only the pairs of the
+// wave-uniform mask sv.shd_mask are tested, free pairs included.
+template <bool ANY, bool SEG = ANY, bool ALLOW = false>
 __device__ __forceinline__ void cluster_query(const SceneView& sv, f3 o, f3 d, float tmin,
                                               float* best, int* id) {
-    for (uint32_t free = sv.pair_free; free != 0u; free &= free - 1u) {
+    for (uint32_t free = ALLOW ? (sv.pair_free & sv.shd_mask) : sv.pair_free; free != 0u; free &= free - 1u) {
         const uint32_t k = (uint32_t)__builtin_ctz(free);
         pair_test_rank<ANY>(sv.pair + kPairF4 * k, k, o, d, tmin, best, id);
     }
-    uint32_t cand = cluster_candidates<SEG>(sv, o, d, tmin, *best);
+    uint32_t cand = cluster_candidates<SEG, ALLOW>(sv, o, d, tmin, *best, ALLOW ? sv.shd_cskip : 0u);
+    if (ALLOW) cand &= sv.shd_mask;
     RT_STAT(12, 1);
     RT_STAT(15, __popcll(__ballot(1)));
 #if RT_CLU_HELP
@@ -1189,7 +1204,14 @@ __device__ __forceinline__ bool any_hit(const SceneView& sv, f3& o, f3& d, float
     if (GEO == kGeoPairClu) {
         float tm = tmax;
         int id = -1;
-        cluster_query<true>(sv, o, d, tmin, &tm, &id);
+        if (RT_SHD_CAND && RT_CAM_CAND && PACKET && sv.shd_avail) {
+            // bounce-0 shadow rays: the wave's occluder mask (rt_shaft.hpp);
+            // the boolean does not depend on which non-occluders are skipped
+            if (sv.shd_mask == 0u) return false;
+            cluster_query<true, true, true>(sv, o, d, tmin, &tm, &id);
+        } else {
+            cluster_query<true>(sv, o, d, tmin, &tm, &id);
+        }
         if (id >= 0) return true;
     } else if (geo_pairs(GEO)) {
         for (uint32_t k = 0; k < sv.nP; ++k) {

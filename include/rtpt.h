@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RTPT_ABI_VERSION 8
+#define RTPT_ABI_VERSION 9
 
 /* Maximum bounce count: Halton dimensions 2+5b..5+5b must stay inside the
  * 24-entry `primes[]` table (`RTrace/sampling.metal:97-104`); b <= 3. */
@@ -396,6 +396,19 @@ int rt_scene_describe_ex(const rt_scene_desc* scene, const rt_create_options* op
  * without pair records gets all ones. */
 int rt_debug_camera_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
                                uint8_t* may_hit);
+
+/* Debug (host-only): which triangles can occlude a bounce-0 shadow ray of that
+ * pixel rectangle (any jitter, any light sample), by the shaft test of
+ * gpuraytracer_amd/csrc/rt_shaft.hpp: the union over every
+ * triangle of every pair in the rectangle's camera mask.  may_occlude: one
+ * byte per triangle id, 1 = the triangle's pair stays in the occluder mask.
+ * *available = 0 when nothing is decided for the rectangle (a grazing or
+ * crossing source plane, no pair records): every byte is then 1.
+ * The box-cluster kernel runs the same test once per wave, but only for a
+ * wave whose camera mask holds exactly one pair; for a wave with more pairs
+ * it runs the generic query whatever this function reports. */
+int rt_debug_shadow_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
+                               uint8_t* may_occlude, int32_t* available);
 
 /* The reference's image epilogue (RTrace/image.swift:35-65): fp16 round trip,
  * ×2 exposure, Reinhard, gamma 1/2.2, clamp, truncating UInt8, alpha 255.
