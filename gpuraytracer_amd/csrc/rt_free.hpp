@@ -162,8 +162,8 @@ __global__ __launch_bounds__(kFreeThreads, kFreeWavesPerEu) void path_free_kerne
     static_assert(GEO == kGeoSphLds || GEO == kGeoTriBvh, "free-running kernel: BVH scenes");
     constexpr bool SPH = GEO == kGeoSphLds;
     // parked leaves are tested once they are >= 1/kLeafDen of the walking lanes
-    // (the lockstep walks' kSphParkDen / kTriParkDen)
-    // (rt_create_options.walk_leaf_den; 1: only when every walker is parked)
+    // (kSphParkDen, or the lockstep triangle walk's kTriParkDen;
+    // rt_create_options.walk_leaf_den; 1: only when every walker is parked)
     const int kLeafDen = P.walk_leaf_den ? (int)P.walk_leaf_den : (SPH ? kSphParkDen : kTriParkDen);
     extern __shared__ float4 lds[];
     __shared__ uint32_t seed_s[kFreeThreads];
@@ -191,21 +191,10 @@ __global__ __launch_bounds__(kFreeThreads, kFreeWavesPerEu) void path_free_kerne
     sv.nTN = P.nTN;
     const uint32_t nLay = SPH ? P.nE : P.nTN;  // entries per octant layout
 
-    // XCD-aware tile order (see path_trace_kernel), one wave = one tile of
-    // 8x8 pixels, or one row of 64 pixels when the rows are interleaved
+    // XCD-aware tile order (xcd_tile), one wave = one tile of 8x8 pixels, or
+    // one row of 64 pixels when the rows are interleaved
     uint32_t bx, by;
-    {
-        constexpr uint32_t kXcdRun = 4;
-        const uint32_t n = gridDim.x * gridDim.y, full = n / (8u * kXcdRun) * (8u * kXcdRun);
-        const uint32_t p = blockIdx.y * gridDim.x + blockIdx.x;
-        uint32_t t = p;
-        if (p < full) {
-            const uint32_t xcd = p % 8u, k = p / 8u;
-            t = ((k / kXcdRun) * 8u + xcd) * kXcdRun + k % kXcdRun;
-        }
-        bx = t % gridDim.x;
-        by = t / gridDim.x;
-    }
+    xcd_tile(bx, by);
     const uint32_t kWX = P.wave_w, kWY = 64u / kWX;
     auto opaque_tid = []() {
         uint32_t t = threadIdx.x;
@@ -446,11 +435,7 @@ __global__ __launch_bounds__(kFreeThreads, kFreeWavesPerEu) void path_free_kerne
                 const float fx = (float)x, fy = (float)(P.row_start + j * P.row_step);
                 const float jx = halton_dim<0, SMALL>(i);                                 // :39-40
                 const float jy = halton_dim<1, SMALL>(i);
-                // generateCameraRay (sampling.metal:125-157)
-                const float sx = ((fx + jx) / fW) * 2.0f - 1.0f;
-                const float ty = -(((fy + jy) / fH) * 2.0f - 1.0f);
-                const float sh = sx * P.halfW, th = ty * P.halfH;
-                d = normalize((cu * sh + cv * th) - cw);
+                d = camera_dir(P, cu, cv, cw, fW, fH, fx, fy, jx, jy);
                 o = ld_f3(P.cam_pos);
                 st_set3(kFsThr, f3{1.0f, 1.0f, 1.0f});
                 st_set3(kFsAcc, f3{0.0f, 0.0f, 0.0f});
@@ -621,10 +606,5 @@ __global__ __launch_bounds__(kFreeThreads, kFreeWavesPerEu) void path_free_kerne
     uint32_t x, j;
     pixel_of(t, x, j);
     const f3 lum = st_get3(kFsLum);
-    const size_t o2 = (size_t)j * (size_t)P.W + x;
-    if (P.sum) P.sum[o2] = make_float4(lum.x, lum.y, lum.z, (float)P.samples_total);
-    if (P.out) {
-        const float fs = (float)P.samples_total;                   // :106
-        store_pixel(P, o2, lum.x / fs, lum.y / fs, lum.z / fs);
-    }
+    finish_pixel(P, (size_t)j * (size_t)P.W + x, lum);
 }

@@ -75,10 +75,6 @@ namespace {
 #ifndef RT_CENSUS
 #define RT_CENSUS 0
 #endif
-// RT_LQ: the light sample point and its cosine without their zero terms (shade)
-#ifndef RT_LQ
-#define RT_LQ 1
-#endif
 template <typename T>
 __device__ __forceinline__ T cz(T v) {
     asm volatile("" : "+v"(v));
@@ -185,7 +181,7 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
     // lcen.y (lcen.z) + +-0 is lcen.y (lcen.z) unless that is -0 -- the
     // host's light_plain flag; otherwise the literal form
     f3 q;
-    if (RT_LQ && P.light_plain)
+    if (P.light_plain)
         q = f3{lcen.x + 0.25f * ux, lcen.y, lcen.z + 0.25f * uy};
     else
         q = (lcen + f3{0.25f, 0.0f, 0.0f} * ux) + f3{0.0f, 0.0f, 0.25f} * uy;
@@ -200,7 +196,7 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
     // dot(-L, (0,-1,0)) = fma(-L.z, 0, fma(-L.y, -1, -L.x * 0)) is L.y exactly
     // when L.y != 0; when L.y is +-0 either form gives a zero, which makes the
     // light term zero (no shadow query, +0 added: the same result)
-    lc = lc * saturate(RT_LQ ? L.y : dot(-L, f3{0.0f, -1.0f, 0.0f}));
+    lc = lc * saturate(L.y);
     lc = lc * saturate(dot(N, L));                         // :75
     s.thr = s.thr * diffuse;                               // :76
     // the light term lc * throughput (:87-89) and the next direction (:93-100)
@@ -220,13 +216,7 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
         d2 = (right * (st * cp) + N * ct) + fwd * (st * sp);  // sampling.metal:65
     }
     if (FUSE && b + 1 < B) {
-        FusedHit h;
-        if constexpr (GEO == kGeoTriBvh) {
-            const bool lit = contrib.x != 0.0f || contrib.y != 0.0f || contrib.z != 0.0f;
-            h = tri_walk_dual(sv, p, L, dist - 1e-3f, lit, d2);
-        } else {
-            h = fused_shadow_closest(sv, p, L, dist - 1e-3f, seg_lo, seg_hi, d2);
-        }
+        const FusedHit h = fused_shadow_closest(sv, p, L, dist - 1e-3f, seg_lo, seg_hi, d2);
         if (!h.occluded) s.acc = s.acc + contrib;          // :79-89
         s.d = d2;
         s.o = p;                                           // :99-100
@@ -244,11 +234,11 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
     const bool lit = (GEO == kGeoTriBvh && b == 0) || contrib.x != 0.0f || contrib.y != 0.0f ||
                      contrib.z != 0.0f;
     if constexpr (STASH) {
-        // the BVH kernels park contrib and the next direction in a per-lane
+        // the sphere kernel parks contrib and the next direction in a per-lane
         // LDS stash across the shadow walk (read back through an opaque lane
         // index, so they are not kept in registers): at 64 VGPRs (8 waves/SIMD)
         // they were 5-6 spilled VGPRs, 24-28 B of scratch per lane (round 4)
-        constexpr uint32_t SS = GEO == kGeoSphLds ? kSphBlockThreads : kBlockThreads;  // stash stride
+        constexpr uint32_t SS = kSphBlockThreads;  // stash stride
         uint32_t t = threadIdx.x;
         asm volatile("" : "+v"(t));
         float* st = sv.xstash;
@@ -288,14 +278,11 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
     return true;
 }
 
+// One bounce b of raytrace.metal:47-101.  Returns false when the path ends.
 // The triangle-BVH kernel runs WITHOUT the LDS stash of shade(): with it the
 // kernel has no scratch (63 VGPRs) but ran 778 vs 846 Msamples/s on 100k
 // triangles (round 5, profiles/r5/ab_results.md); without it 18 VGPRs spill
 // (16 B of scratch per lane, L2-resident)
-#ifndef RT_TRI_STASH
-#define RT_TRI_STASH 0
-#endif
-// One bounce b of raytrace.metal:47-101.  Returns false when the path ends.
 template <int b, int B, int GEO, bool SPH, bool SMALL>
 __device__ __forceinline__ bool bounce(const KParams& P, const SceneView& sv, PathState& s) {
     float t = 1000.0f;                                      // max_distance (sampling.metal:155)
@@ -310,8 +297,7 @@ __device__ __forceinline__ bool bounce(const KParams& P, const SceneView& sv, Pa
     }
 #endif
     if (id < 0) return false;                               // :51-53
-    return shade<b, B, GEO, SPH, SMALL, false, GEO == kGeoSphLds || (RT_TRI_STASH && GEO == kGeoTriBvh)>(P, sv, s, id,
-                                                                                                 t);
+    return shade<b, B, GEO, SPH, SMALL, false, GEO == kGeoSphLds>(P, sv, s, id, t);
 }
 
 template <int b, int B, int GEO, bool SPH, bool SMALL>
@@ -364,43 +350,8 @@ struct FusedChain<B, B, GEO, SMALL> {
 // closest hit of bounce b + 1 (fused_shadow_closest).  The box-cluster kernel
 // does not: its fused candidate rounds measured 5 % slower on Cornell 1080p
 // (DESIGN.md §5).
-// Triangle-BVH chain with the dual walks (RT_TRI_DUAL): bounce 0 as usual
-// (packet walks), then for b >= 1 the shadow query of b and the closest hit of
-// b + 1 in one tri_walk_dual loop.
-template <int b, int B, bool SMALL>
-struct TriDualChain {
-    __device__ __forceinline__ static void run(const KParams& P, const SceneView& sv, PathState& s, int id,
-                                               float t) {
-        if constexpr (b + 1 < B) {
-            int nid = -1;
-            float nt = 0.0f;
-            if (!shade<b, B, kGeoTriBvh, false, SMALL, true>(P, sv, s, id, t, &nid, &nt)) return;
-            if (nid >= 0) TriDualChain<b + 1, B, SMALL>::run(P, sv, s, nid, nt);
-        } else {
-            (void)shade<b, B, kGeoTriBvh, false, SMALL>(P, sv, s, id, t);
-        }
-    }
-};
-template <int B, bool SMALL>
-struct TriDualChain<B, B, SMALL> {
-    __device__ __forceinline__ static void run(const KParams&, const SceneView&, PathState&, int, float) {}
-};
-
-#ifndef RT_TRI_DUAL
-#define RT_TRI_DUAL 0
-#endif
-
 template <int B, int GEO, bool SPH, bool SMALL>
 __device__ __forceinline__ void trace_path(const KParams& P, const SceneView& sv, PathState& s) {
-    if constexpr (RT_TRI_DUAL && GEO == kGeoTriBvh && !SPH && B > 1) {
-        float t = 1000.0f;                                  // sampling.metal:155
-        const int id = closest_hit<GEO, false, true, 0>(sv, s.o, s.d, 0.001f, &t);
-        if (id < 0 || !shade<0, B, GEO, false, SMALL>(P, sv, s, id, t)) return;
-        float t1 = 1000.0f;
-        const int id1 = closest_hit<GEO, false, false, 1>(sv, s.o, s.d, 0.001f, &t1);
-        if (id1 >= 0) TriDualChain<1, B, SMALL>::run(P, sv, s, id1, t1);
-        return;
-    }
     if (geo_pairs(GEO) && !SPH && B > 1) {
         float t = 1000.0f;                                  // sampling.metal:155
         const int id = closest_hit<GEO, false, true, 0>(sv, s.o, s.d, 0.001f, &t);
@@ -455,6 +406,50 @@ __device__ __forceinline__ void store_pixel(const KParams& P, size_t o, float r,
     } else {
         reinterpret_cast<float4*>(P.out)[o] = make_float4(r, g, b, 1.0f);
     }
+}
+
+// The end of a pixel (raytrace.metal:106-109): its running sum to P.sum, the
+// mean over all samples so far to the image.
+__device__ __forceinline__ void finish_pixel(const KParams& P, size_t o, f3 lum) {
+    if (P.sum) P.sum[o] = make_float4(lum.x, lum.y, lum.z, (float)P.samples_total);
+    if (P.out) {
+        const float fs = (float)P.samples_total;                 // :106
+        const float r = lum.x / fs, g = lum.y / fs, bl = lum.z / fs;
+        store_pixel(P, o, r, g, bl);
+    }
+}
+
+// generateCameraRay (sampling.metal:125-157): the direction through pixel
+// (fx, fy) jittered by (jx, jy).  IEEE: the triangle-BVH kernel's
+// normalize_ieee (rt_math.h).
+template <bool IEEE = false>
+__device__ __forceinline__ f3 camera_dir(const KParams& P, f3 cu, f3 cv, f3 cw, float fW, float fH, float fx,
+                                         float fy, float jx, float jy) {
+    const float sx = ((fx + jx) / fW) * 2.0f - 1.0f;
+    const float ty = -(((fy + jy) / fH) * 2.0f - 1.0f);
+    const float sh = sx * P.halfW, th = ty * P.halfH;
+    return IEEE ? normalize_ieee((cu * sh + cv * th) - cw) : normalize((cu * sh + cv * th) - cw);
+}
+
+// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs in
+// dispatch order (p = blockIdx.y * gridDim.x + blockIdx.x; MI355X_MICROARCH.md
+// "Workgroup dispatch"), so the tiles are dealt in runs of kXcdRun: the run
+// of neighbouring tiles that share the 128-B lines of the seed rows goes
+// through ONE XCD's L2 (seed reads 4x -> 1x the seed bytes), while the runs
+// still interleave over the XCDs, which keeps the cheap and the expensive
+// image regions evenly spread (contiguous bands per XCD ran 7 % slower).
+// Speed only: every tile is rendered exactly once.
+__device__ __forceinline__ void xcd_tile(uint32_t& bx, uint32_t& by) {
+    constexpr uint32_t kXcdRun = 4;  // runs of 0 (plain order) / 16: 158.9 / 157.6 vs 158.4 ms on config 4
+    const uint32_t n = gridDim.x * gridDim.y, full = n / (8u * kXcdRun + (kXcdRun == 0)) * (8u * kXcdRun);
+    const uint32_t p = blockIdx.y * gridDim.x + blockIdx.x;
+    uint32_t t = p;
+    if (kXcdRun > 0 && p < full) {
+        const uint32_t xcd = p % 8u, k = p / 8u;
+        t = ((k / kXcdRun) * 8u + xcd) * kXcdRun + k % kXcdRun;
+    }
+    bx = t % gridDim.x;
+    by = t / gridDim.x;
 }
 
 // ---- sorted-path variant ----------------------------------------------------
@@ -554,7 +549,7 @@ __device__ __forceinline__ void deliver(float4* lds, uint32_t owner, f3 acc) {
 
 // GEO: kGeoPairLds (pair records in LDS, wave-culled loops), kGeoTriBvh
 // (triangle BVH: camera rays as wave packets, bounce rays per lane) or
-// kGeoSphLds (the room's pairs in LDS + the compact sphere BVH).  For the BVH
+// kGeoSphLds (the room's pairs in LDS + the leaf-box sphere BVH).  For the BVH
 // scenes the sort is what the lockstep kernels lack: the waves of a bounce
 // walk rays of ONE direction octant, i.e. ONE of the eight BVH layouts.
 template <int b, int B, int GEO, bool SPH, bool SMALL>
@@ -638,9 +633,7 @@ void path_trace_kernel(KParams P) {
         RT_LDS_GUARD(16 * (size_t)(ng4 + (GEO == kGeoPairClu ? kCluF4 * P.nC : 0u)) +
                      (GEO == kGeoPairClu ? 4 * (size_t)kHaltonTabFloats : 0));
         for (uint32_t k = threadIdx.x; k < ng4; k += NT) lds[k] = src[k];
-        if (GEO == kGeoSphLds) {  // the compact sphere BVH (8 layouts) stays in global memory (L2)
-            sv.sent = reinterpret_cast<const uint4*>(P.sph_lds);
-            sv.sid = P.sph_lds_id;
+        if (GEO == kGeoSphLds) {  // the leaf-box sphere BVH (8 layouts) stays in global memory (L2)
             sv.sbox = P.sph_box;
             sv.nSB = P.nN;
             __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
@@ -663,44 +656,20 @@ void path_trace_kernel(KParams P) {
         sv.tri = P.tri_isect;
         sv.pair = nullptr;
     }
-    if (GEO == kGeoTriBvh && RT_TRI_STASH) {  // per-lane stash of shade() across the shadow walks
-        __shared__ float tri_stash[GEO == kGeoTriBvh && RT_TRI_STASH ? 6 * kBlockThreads : 1];
-        sv.xstash = tri_stash;
-    }
     sv.tnode = P.tri_nodes;
     sv.tsorted = P.tri_sorted;
     sv.tperm = P.tri_perm;
     sv.nTN = P.nTN;
     sv.node = P.sph_nodes;  // sphere BVH: scalar loads from global memory
     sv.sph = P.sph_isect;
-    // sphere walks: BVH nodes per layout (global walks) or compact LDS entries
-    sv.nN = SPH ? (GEO == kGeoSphLds ? P.nE : P.nN) : 0u;
+    sv.nN = SPH ? P.nN : 0u;  // sphere walks: BVH nodes per layout
     sv.sph_perm = P.sph_perm;
 
     // wave = 64/L pixels: 8x8 (L=1), 4x4 (L=4), 2x2 (L=16), or one row of 64/L
     // pixels for interleaved rows (launcher's wave_w); workgroup = 2x2 waves
     const uint32_t kWX = (L == 1) ? 8u : P.wave_w, kWY = (64u / L) / kWX;
-    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs in
-    // dispatch order (p = blockIdx.y * gridDim.x + blockIdx.x; MI355X_MICROARCH.md
-    // "Workgroup dispatch"), so the tiles are dealt in runs of kXcdRun: the run
-    // of neighbouring tiles that share the 128-B lines of the seed rows goes
-    // through ONE XCD's L2 (seed reads 4x -> 1x the seed bytes), while the runs
-    // still interleave over the XCDs, which keeps the cheap and the expensive
-    // image regions evenly spread (contiguous bands per XCD ran 7 % slower).
-    // Speed only: every tile is rendered exactly once.
     uint32_t bx, by;
-    {
-        constexpr uint32_t kXcdRun = 4;  // runs of 0 (plain order) / 16: 158.9 / 157.6 vs 158.4 ms on config 4
-        const uint32_t n = gridDim.x * gridDim.y, full = n / (8u * kXcdRun + (kXcdRun == 0)) * (8u * kXcdRun);
-        const uint32_t p = blockIdx.y * gridDim.x + blockIdx.x;
-        uint32_t t = p;
-        if (kXcdRun > 0 && p < full) {
-            const uint32_t xcd = p % 8u, k = p / 8u;
-            t = ((k / kXcdRun) * 8u + xcd) * kXcdRun + k % kXcdRun;
-        }
-        bx = t % gridDim.x;
-        by = t / gridDim.x;
-    }
+    xcd_tile(bx, by);
     auto pixel_of = [&](uint32_t t, uint32_t& x, uint32_t& j) {
         const uint32_t lane = t & 63u, wave = t >> 6, pix = lane / L;
         x = bx * (WR * kWX) + (wave % WR) * kWX + (pix % kWX);
@@ -820,11 +789,7 @@ void path_trace_kernel(KParams P) {
             s.i = seed_s[t] + n;                                 // seed + (sample_base + n)
             const float jx = halton_dim<0, SMALL>(s.i);                                // :39-40
             const float jy = halton_dim<1, SMALL, GEO == kGeoPairClu>(s.i, sv.htab);
-            // generateCameraRay (sampling.metal:125-157)
-            const float sx = ((fx + jx) / fW) * 2.0f - 1.0f;
-            const float ty = -(((fy + jy) / fH) * 2.0f - 1.0f);
-            const float sh = sx * P.halfW, th = ty * P.halfH;
-            s.d = GEO != kGeoTriBvh ? normalize((cu * sh + cv * th) - cw) : normalize_ieee((cu * sh + cv * th) - cw);
+            s.d = camera_dir<GEO == kGeoTriBvh>(P, cu, cv, cw, fW, fH, fx, fy, jx, jy);
             s.o = ld_f3(P.cam_pos);
             s.thr = f3{1.0f, 1.0f, 1.0f};
 #if RT_CENSUS == 1
@@ -832,9 +797,7 @@ void path_trace_kernel(KParams P) {
                 const uint32_t i2 = cz(s.i);
                 const float jx2 = halton_dim<0, SMALL>(i2);
                 const float jy2 = halton_dim<1, SMALL, GEO == kGeoPairClu>(i2, sv.htab);
-                const float sx2 = ((cz(fx) + jx2) / fW) * 2.0f - 1.0f;
-                const float ty2 = -(((cz(fy) + jy2) / fH) * 2.0f - 1.0f);
-                cz_sink(normalize((cu * (sx2 * P.halfW) + cv * (ty2 * P.halfH)) - cw));
+                cz_sink(camera_dir(P, cu, cv, cw, fW, fH, cz(fx), cz(fy), jx2, jy2));
             }
 #endif
 #ifndef RT_TIMING_NO_TRACE  // timing-only A/B (tools/ab_kernel.sh): camera, Halton jitter and sums alone
@@ -845,10 +808,7 @@ void path_trace_kernel(KParams P) {
         }
         if (L == 1) {
             lum = lum + s.acc;                                   // :103
-#ifndef RT_SPH_DPP
-#define RT_SPH_DPP 0
-#endif
-        } else if (L <= 16 && (!SPH || RT_SPH_DPP)) {
+        } else if (L <= 16 && !SPH) {
             // a pixel's L lanes are consecutive lanes of one 16-lane DPP row
             // (L = 4: groups at 0, 4, 8, 12; L = 16: the whole row), so its
             // leader reads sample r*L + k from lane +k with a row shift fused
@@ -906,6 +866,8 @@ void path_trace_kernel(KParams P) {
     }
     uint32_t x, j;
     pixel_of(t, x, j);
+    // finish_pixel, spelled out: the call compiles to another branch order in
+    // the L = 1 kernels
     const size_t o = (size_t)j * (size_t)P.W + x;
     if (P.sum) P.sum[o] = make_float4(lum.x, lum.y, lum.z, (float)P.samples_total);
     if (P.out) {
@@ -937,9 +899,7 @@ void path_trace_sorted_kernel(
     RT_LDS_GUARD(16 * (size_t)(kSortF4 + ng4));
     float4* scene = lds + kSortF4;  // sort buffers first: compile-time offsets
     for (uint32_t k = threadIdx.x; k < ng4; k += kBlockThreads) scene[k] = P.pair_isect[k];
-    sv.nN = SPH ? (GEO == kGeoSphLds ? P.nE : P.nN) : 0u;
-    sv.sent = reinterpret_cast<const uint4*>(P.sph_lds);
-    sv.sid = P.sph_lds_id;
+    sv.nN = SPH ? P.nN : 0u;
     sv.sbox = P.sph_box;
     sv.nSB = P.nN;
     sv.tnode = P.tri_nodes;
@@ -978,10 +938,7 @@ void path_trace_sorted_kernel(
         s.d = f3{0.0f, 0.0f, 0.0f};
         if (valid) {
             const float jx = halton_dim<0, SMALL>(s.i), jy = halton_dim<1, SMALL>(s.i);
-            const float sx = ((fx + jx) / fW) * 2.0f - 1.0f;
-            const float ty = -(((fy + jy) / fH) * 2.0f - 1.0f);
-            const float sh = sx * P.halfW, th = ty * P.halfH;
-            s.d = normalize((ld_f3(P.cam_u) * sh + ld_f3(P.cam_v) * th) - ld_f3(P.cam_w));
+            s.d = camera_dir(P, ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), fW, fH, fx, fy, jx, jy);
         }
         uint32_t owner = tid;
         bool alive = valid;
@@ -989,13 +946,7 @@ void path_trace_sorted_kernel(
         __syncthreads();  // sample n's hand-offs land before sample n+1's
     }
     if (!valid) return;
-    const f3 lum{sum[tid], sum[kBlockThreads + tid], sum[2 * kBlockThreads + tid]};
-    if (P.sum) P.sum[o] = make_float4(lum.x, lum.y, lum.z, (float)P.samples_total);
-    if (P.out) {
-        const float fs = (float)P.samples_total;                 // :106
-        const float r = lum.x / fs, g = lum.y / fs, bl = lum.z / fs;
-        store_pixel(P, o, r, g, bl);
-    }
+    finish_pixel(P, o, f3{sum[tid], sum[kBlockThreads + tid], sum[2 * kBlockThreads + tid]});
 }
 
 // rt_math_selfcheck: the shipped sqrt_cr / rcp_cr (rt_math.h) against the
@@ -1128,21 +1079,22 @@ inline hipError_t allow_lds(const void* kernel, size_t bytes) {
 template <int B, int GEO, bool SPH, bool SMALL, int L>
 hipError_t launch_tl(const KParams& P, size_t lds_bytes, hipStream_t stream) {
     KParams Q = P;
-    // wave tile: compact (4x4, 2x2) for whole frames; one row of 64/L pixels
-    // when the rows are interleaved (row_step > 1), which keeps a wave's camera
-    // rays adjacent in the image (N = 8 share: 10,822 -> 11,211 Msamples/s)
-    Q.wave_w = (P.row_step > 1) ? 64u / L : (L == 4 ? 4u : 2u);
+    // wave tile: 8x8 pixels at one lane per pixel; L > 1: compact (4x4, 2x2)
+    // for whole frames, one row of 64/L pixels when the rows are interleaved
+    // (row_step > 1), which keeps a wave's camera rays adjacent in the image
+    // (N = 8 share: 10,822 -> 11,211 Msamples/s)
+    if (L > 1) Q.wave_w = (P.row_step > 1) ? 64u / L : (L == 4 ? 4u : 2u);
     constexpr uint32_t WR = waves_per_row(GEO), WC = waves_per_col(GEO);
-    const uint32_t TX = WR * Q.wave_w, TY = WC * ((64u / L) / Q.wave_w);
+    const uint32_t WX = (L == 1) ? 8u : Q.wave_w;
+    const uint32_t TX = WR * WX, TY = WC * ((64u / L) / WX);
     const dim3 grid((P.W + TX - 1) / TX, (P.row_count + TY - 1) / TY);
     if (GEO == kGeoSphLds) {
         const hipError_t e = allow_lds((const void*)path_trace_kernel<B, GEO, SPH, SMALL, L>, lds_bytes);
         if (e != hipSuccess) return e;
     }
-    const size_t lds = lds_bytes;  // staged_lds_bytes of the layout
-    note_launch<B, GEO, SPH, SMALL, L>("path_trace_kernel", Q, grid, block_threads(GEO), lds);
+    note_launch<B, GEO, SPH, SMALL, L>("path_trace_kernel", Q, grid, block_threads(GEO), lds_bytes);
     hipLaunchKernelGGL((path_trace_kernel<B, GEO, SPH, SMALL, L>), grid, dim3(block_threads(GEO)),
-                       lds, stream, Q);
+                       lds_bytes, stream, Q);  // staged_lds_bytes of the layout
     return hipGetLastError();
 }
 
@@ -1153,33 +1105,7 @@ hipError_t launch_t(const KParams& P, size_t lds_bytes, hipStream_t stream) {
         if (lpp == 16) return launch_tl<B, GEO, SPH, SMALL, 16>(P, lds_bytes, stream);
         if (lpp == 4) return launch_tl<B, GEO, SPH, SMALL, 4>(P, lds_bytes, stream);
     }
-    constexpr uint32_t TX = 8u * waves_per_row(GEO), TY = 8u * waves_per_col(GEO);  // 8x8-pixel waves
-    const dim3 grid((P.W + TX - 1) / TX, (P.row_count + TY - 1) / TY);
-    if (GEO == kGeoSphLds) {
-        const hipError_t e = allow_lds((const void*)path_trace_kernel<B, GEO, SPH, SMALL>, lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    const size_t lds = lds_bytes;  // staged_lds_bytes of the layout
-    note_launch<B, GEO, SPH, SMALL, 1>("path_trace_kernel", P, grid, block_threads(GEO), lds);
-    hipLaunchKernelGGL((path_trace_kernel<B, GEO, SPH, SMALL>), grid, dim3(block_threads(GEO)),
-                       lds, stream, P);
-    return hipGetLastError();
-}
-
-template <int B, int GEO>
-hipError_t launch_g(const KParams& P, size_t lds_bytes, hipStream_t stream) {
-    const bool small = P.max_index < kSmallIndexMax;
-    if constexpr (GEO == kGeoPairClu)  // triangle-only scenes (launch_path_trace)
-        return small ? launch_t<B, GEO, false, true>(P, lds_bytes, stream)
-                     : launch_t<B, GEO, false, false>(P, lds_bytes, stream);
-    if constexpr (GEO == kGeoSphLds)  // sphere scenes only
-        return small ? launch_t<B, GEO, true, true>(P, lds_bytes, stream)
-                     : launch_t<B, GEO, true, false>(P, lds_bytes, stream);
-    if (P.nS > 0)
-        return small ? launch_t<B, GEO, true, true>(P, lds_bytes, stream)
-                     : launch_t<B, GEO, true, false>(P, lds_bytes, stream);
-    return small ? launch_t<B, GEO, false, true>(P, lds_bytes, stream)
-                 : launch_t<B, GEO, false, false>(P, lds_bytes, stream);
+    return launch_tl<B, GEO, SPH, SMALL, 1>(P, lds_bytes, stream);
 }
 
 template <int B, int GEO, bool SPH, bool SMALL>
@@ -1187,25 +1113,36 @@ hipError_t launch_sorted_t(const KParams& P, size_t lds_bytes, hipStream_t strea
     const dim3 grid((P.W + kTile - 1) / kTile, (P.row_count + kTile - 1) / kTile);
     note_launch<B, GEO, SPH, SMALL, 1>("path_trace_sorted_kernel", P, grid, kBlockThreads, lds_bytes);
     hipLaunchKernelGGL((path_trace_sorted_kernel<B, GEO, SPH, SMALL>), grid, dim3(kBlockThreads),
-                       lds_bytes, stream, P);
+                       lds_bytes, stream, P);  // staged_lds_bytes: path buffers + scene records
     return hipGetLastError();
 }
 
-template <int B, int GEO>
-hipError_t launch_sorted_g(const KParams& P, size_t lds_bytes, hipStream_t stream) {
-    const bool small = P.max_index < kSmallIndexMax;
-    const size_t bytes = lds_bytes;  // staged_lds_bytes: path buffers + scene records
-    if constexpr (GEO == kGeoSphLds)
-        return small ? launch_sorted_t<B, GEO, true, true>(P, bytes, stream)
-                     : launch_sorted_t<B, GEO, true, false>(P, bytes, stream);
-    if constexpr (GEO == kGeoTriBvh)
-        return small ? launch_sorted_t<B, GEO, false, true>(P, bytes, stream)
-                     : launch_sorted_t<B, GEO, false, false>(P, bytes, stream);
-    if (P.nS > 0)
-        return small ? launch_sorted_t<B, GEO, true, true>(P, bytes, stream)
-                     : launch_sorted_t<B, GEO, true, false>(P, bytes, stream);
-    return small ? launch_sorted_t<B, GEO, false, true>(P, bytes, stream)
-                 : launch_sorted_t<B, GEO, false, false>(P, bytes, stream);
+template <int B, int GEO, bool SORTED, bool SPH, bool SMALL>
+hipError_t launch_k(const KParams& P, size_t lds_bytes, hipStream_t stream) {
+    if constexpr (SORTED)
+        return launch_sorted_t<B, GEO, SPH, SMALL>(P, lds_bytes, stream);
+    else
+        return launch_t<B, GEO, SPH, SMALL>(P, lds_bytes, stream);
+}
+
+template <int B, int GEO, bool SORTED, bool SPH>
+hipError_t launch_h(const KParams& P, size_t lds_bytes, hipStream_t stream) {
+    return P.max_index < kSmallIndexMax ? launch_k<B, GEO, SORTED, SPH, true>(P, lds_bytes, stream)
+                                        : launch_k<B, GEO, SORTED, SPH, false>(P, lds_bytes, stream);
+}
+
+// Picks the sphere and Halton forms of the lockstep (SORTED = false) or the
+// octant-sorted kernel.  The box-cluster layout and the sorted triangle BVH
+// are chosen for triangle-only scenes, kGeoSphLds for sphere scenes only
+// (choose_kernel), whatever P.nS says.  Every layout still instantiates both
+// sphere forms, in this order: the code object's kernels and their order are
+// those of the two pickers this replaces (tools/isa_diff.sh).
+template <int B, int GEO, bool SORTED = false>
+hipError_t launch_g(const KParams& P, size_t lds_bytes, hipStream_t stream) {
+    if constexpr (GEO == (SORTED ? kGeoTriBvh : kGeoPairClu))
+        return launch_h<B, GEO, SORTED, false>(P, lds_bytes, stream);
+    if (GEO == kGeoSphLds || P.nS > 0) return launch_h<B, GEO, SORTED, true>(P, lds_bytes, stream);
+    return launch_h<B, GEO, SORTED, false>(P, lds_bytes, stream);
 }
 
 // The free-running kernel (rt_free.hpp): one pixel per lane, 8x8-pixel waves
@@ -1216,9 +1153,9 @@ hipError_t launch_free_t(const KParams& P, size_t lds_bytes, hipStream_t stream)
     Q.wave_w = (P.row_step > 1) ? 64u : 8u;
     const uint32_t TY = 64u / Q.wave_w;
     const dim3 grid((P.W + Q.wave_w - 1) / Q.wave_w, (P.row_count + TY - 1) / TY);
-    const size_t lds = lds_bytes;  // staged_lds_bytes of the layout
-    note_launch<B, GEO, GEO == kGeoSphLds, SMALL, 1>("path_free_kernel", Q, grid, kFreeThreads, lds);
-    hipLaunchKernelGGL((path_free_kernel<B, GEO, SMALL>), grid, dim3(kFreeThreads), lds, stream, Q);
+    note_launch<B, GEO, GEO == kGeoSphLds, SMALL, 1>("path_free_kernel", Q, grid, kFreeThreads, lds_bytes);
+    hipLaunchKernelGGL((path_free_kernel<B, GEO, SMALL>), grid, dim3(kFreeThreads), lds_bytes, stream,
+                       Q);  // staged_lds_bytes of the layout
     return hipGetLastError();
 }
 
@@ -1236,9 +1173,9 @@ template <int B>
 hipError_t launch_b(const KParams& P, int geo, size_t lds_bytes, hipStream_t stream) {
     if (geo == kGeoFreeSph) return launch_free<B, kGeoSphLds>(P, lds_bytes, stream);
     if (geo == kGeoFreeTri) return launch_free<B, kGeoTriBvh>(P, lds_bytes, stream);
-    if (geo == kGeoPairSorted) return launch_sorted_g<B, kGeoPairLds>(P, lds_bytes, stream);
-    if (geo == kGeoSortSph) return launch_sorted_g<B, kGeoSphLds>(P, lds_bytes, stream);
-    if (geo == kGeoSortTri) return launch_sorted_g<B, kGeoTriBvh>(P, lds_bytes, stream);
+    if (geo == kGeoPairSorted) return launch_g<B, kGeoPairLds, true>(P, lds_bytes, stream);
+    if (geo == kGeoSortSph) return launch_g<B, kGeoSphLds, true>(P, lds_bytes, stream);
+    if (geo == kGeoSortTri) return launch_g<B, kGeoTriBvh, true>(P, lds_bytes, stream);
     switch (geo) {
         case kGeoPairLds: return launch_g<B, kGeoPairLds>(P, lds_bytes, stream);
         case kGeoPairClu: return launch_g<B, kGeoPairClu>(P, lds_bytes, stream);
@@ -1269,7 +1206,7 @@ KernelChoice choose_kernel(uint32_t nT, uint32_t nP, uint32_t nS, uint32_t nC, u
     // triangle BVH whenever rt_create built one (kTriBvhMinTriangles or no LDS fit),
     // unless another layout is forced
     if (nTN > 0 && (mem == SceneMem::kTriBvh || mem == SceneMem::kAuto)) geo = kGeoTriBvh;
-    // the sphere kernel (one-wave workgroups, compact BVH in L2) while its
+    // the sphere kernel (one-wave workgroups, its BVH in L2) while its
     // per-workgroup copy of the pair records is small (rt_kernel.hpp)
     if (geo == kGeoPairLds && nS > 0 && sph_compact && mem == SceneMem::kAuto &&
         lds(kGeoSphLds) <= kSphPairLdsMaxBytes)
@@ -1311,8 +1248,8 @@ hipError_t launch_path_trace_impl(const KParams& P, uint32_t bounces, SceneMem m
     if (bounces != 3) return hipErrorInvalidValue;
     if (geo == kGeoFreeSph) return launch_free<3, kGeoSphLds>(P, lds_req, stream);
     if (geo == kGeoFreeTri) return launch_free<3, kGeoTriBvh>(P, lds_req, stream);
-    if (geo == kGeoSortSph) return launch_sorted_g<3, kGeoSphLds>(P, lds_req, stream);
-    if (geo == kGeoSortTri) return launch_sorted_g<3, kGeoTriBvh>(P, lds_req, stream);
+    if (geo == kGeoSortSph) return launch_g<3, kGeoSphLds, true>(P, lds_req, stream);
+    if (geo == kGeoSortTri) return launch_g<3, kGeoTriBvh, true>(P, lds_req, stream);
     if (geo == kGeoTriBvh) return launch_g<3, kGeoTriBvh>(P, lds_req, stream);
     return geo == kGeoPairClu ? launch_g<3, kGeoPairClu>(P, lds_req, stream)
                               : launch_g<3, kGeoSphLds>(P, lds_req, stream);

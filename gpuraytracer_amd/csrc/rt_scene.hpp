@@ -125,20 +125,16 @@ struct CompiledScene {
     std::vector<MisShade> mis_shade;    // by triangle id
 };
 
-// The walks of the compact sphere kernel (kGeoSphLds and its free and sorted
-// forms) read the leaf-box layout unless built with -DRT_SPH_LEAFBOX=0
-// (rt_trace.hpp holds the same default).
-#ifndef RT_SPH_LEAFBOX
-#define RT_SPH_LEAFBOX 1
-#endif
-// Whether the compact sphere kernel can run this scene: every table its walks
-// read exists.  build_sphere_box refuses trees that build_sphere_lds accepts
+// Whether the sphere kernel (kGeoSphLds and its free and sorted forms) can
+// run this scene: every table its walks read exists -- the leaf-box layout of
+// the lockstep and sorted walks, the compact entries of the free-running one.
+// build_sphere_box refuses trees that build_sphere_lds accepts
 // (a leaf of more than 128 spheres: the entry stores count - 1 in 7 bits; a
 // non-finite leaf box), and such scenes take the pair kernel with the 32-B-node
 // walk.  THE predicate of the launcher's arguments (rt_api.cpp), of
 // rt_scene_describe_ex's kernel_layout and of sphere_kernel_lds_bytes.
 inline bool sphere_compact_usable(const CompiledScene& s) {
-    return !s.sph_lds.empty() && (!RT_SPH_LEAFBOX || !s.sph_box.empty());
+    return !s.sph_lds.empty() && !s.sph_box.empty();
 }
 
 constexpr uint32_t kTriLeafMax = 1;  // triangles per leaf of the host SAH build (default)

@@ -115,10 +115,10 @@ __device__ __forceinline__ bool sph_test(const float4& S, f3 o, f3 d, float a, f
 // tested, [4q+2] active lanes summed over tested records, [4q+3] division blocks.
 // Box-cluster queries: [12] queries per wave, [13] candidate rounds per wave,
 // [14] lanes summed over rounds, [15] lanes summed over queries.
-// Sphere walks (sphere_walk), base 16 closest / 24 any-hit: [+0] walks per
-// wave, [+1] lanes summed over walks, [+2] walk-loop iterations, [+3] lanes
-// summed over them, [+4] unused, [+5] root rounds, [+6] parked lanes summed
-// over them.
+// Per-lane BVH walks (sphere_walk_box, tri_cbvh_walk), base 16 closest / 24
+// any-hit: [+0] walks per wave, [+1] lanes summed over walks, [+2] walk
+// steps, [+3] lanes summed over them, [+4] unused, [+5] leaf rounds, [+6]
+// parked lanes summed over them.
 #ifdef RT_STATS
 __device__ unsigned long long g_rt_stats[32];
 __device__ __forceinline__ void stat_wave(int slot, unsigned long long v) {
@@ -138,7 +138,7 @@ enum Geo : int {
     kGeoTriBvh = 5,     // GPU-built triangle BVH (rt_lbvh.hip), records from global
     kGeoTriGlobal = 2,  // single-triangle records read from global (big scenes)
     kGeoPairClu = 6,    // pair records in LDS + box clusters
-    kGeoSphLds = 7,     // pair records in LDS + the compact sphere BVH in L2 (one-wave workgroups)
+    kGeoSphLds = 7,     // pair records in LDS + the leaf-box sphere BVH in L2 (one-wave workgroups)
 };
 
 constexpr bool geo_pairs(int g) { return g == kGeoPairLds || g == kGeoPairSmem || g == kGeoSphLds; }
@@ -163,9 +163,9 @@ struct SceneView {
     uint32_t shd_cskip = 0;   // wave-uniform: box clusters none of whose faces is in shd_mask
     bool shd_avail = false;   // shd_mask was computed (a mask of 0: no shadow ray is occluded)
     const float* htab;       // Halton low-digit tables in LDS (kGeoPairClu)
-    const uint4* sent;        // compact sphere BVH entries (kGeoSphLds): 8 octant layouts, global
+    const uint4* sent;        // compact sphere BVH entries (the free-running kernel): 8 octant layouts, global
     const uint16_t* sid;      // sphere id of each compact entry (leaves), global
-    const uint4* sbox;        // the sphere BVH with leaf boxes (RT_SPH_LEAFBOX): 8 layouts of nSB entries
+    const uint4* sbox;        // the sphere BVH with leaf boxes (kGeoSphLds): 8 layouts of nSB entries
     uint32_t nSB;
     const float4* shade;      // MIS shading records, 3 float4 per triangle (rt_mis.hip)
     float* xstash;            // MIS: per-lane primary hit (p, din), SoA in LDS (rt_mis.hip)
@@ -242,7 +242,7 @@ __device__ __forceinline__ uint32_t wave_uniform(uint32_t v) {
 }
 
 // Sphere-BVH walks over the 32-B nodes (the sphere scenes of the pair, single
-// and global layouts; the default sphere kernel walks the compact BVH below).
+// and global layouts; the sphere kernel walks the leaf-box BVH below).
 // One stackless depth-first walk per lane through the escape-index tree of
 // the ray's direction octant (near child first); a node is entered when the
 // ray may hit its padded box.  Candidates are ranked by (t, sphere id) exactly
@@ -341,181 +341,50 @@ __device__ __forceinline__ bool lds_node_hit_nf(const uint4& e, const RayBox& rb
     return vmax3(nx, ny, vmax(nz, tmin)) <= vmin3(fx, fy, vmin(fz, tmax));
 }
 
-// Per-lane walk of the compact sphere BVH with POSTPONED ROOTS (DESIGN.md
-// §3.10; after Aila & Laine's postponed leaf processing, stackless form).
-// Each lane walks the layout of its ray's direction octant.  Each step of a
-// lane is cheap and of similar cost whatever the entry: a near/far box test
-// for an inner node, the discriminant of sph_test for a leaf.  A leaf whose
-// discriminant is positive (a real hit candidate) parks the lane with (b, disc);
-// the others walk on until at least 1/kSphParkDen of the lanes still
-// walking are parked (or none can move), then the wave runs the expensive part
-// of the sphere test -- the IEEE sqrt and divisions -- for all parked lanes
-// together.  Per lane the entries are visited in the same order and every
-// value is sph_test's, ranked by (t, id): the same result.  ANY: *id becomes
-// >= 0 on the first accepted hit (and that lane stops).
-// the parked roots run once they are >= 1/kSphParkDen of the live lanes
-// (config 4: 2 157.3 ms, 4 158.4, 6 161.1; round 5: 3 149.7-149.8, 2 150.2-150.3,
-// 1 207.4 -- 1/2 kept: with 1/3 the profiled HBM traffic rose from 69 to 110 MB)
+// One step of a lane's walk over near/far entries (tri_cbvh_walk;
+// sphere_walk_box takes the same step) in select form: a leaf whose box is
+// hit is parked in `leaf` (its word), a missed inner node is left by its
+// escape index, everything else goes on to the next entry.
+__device__ __forceinline__ void cbvh_step(const uint4* __restrict__ ent, uint32_t& idx, uint32_t& leaf,
+                                          const RayBox& rb, float tmin, float best) {
+    const uint4 e = ent[idx];
+    const bool inner = (e.w & 0x80000000u) != 0u;
+    const bool h = lds_node_hit_nf(e, rb, tmin, best);
+    leaf = (h && !inner) ? e.w : leaf;
+    idx = (h || !inner) ? idx + 1 : (e.w & 0x7FFFFFFFu);
+}
+
+// The free-running kernel (rt_free.hpp) walks the compact entries, where a
+// leaf is the sphere itself, and tests the parked lanes' roots once they are
+// >= 1/kSphParkDen of the walking lanes (config 4, a lockstep walk of the
+// same entries: 2 157.3 ms, 4 158.4, 6 161.1; round 5: 3 149.7-149.8,
+// 2 150.2-150.3, 1 207.4 -- 1/2 kept: with 1/3 the profiled HBM traffic rose
+// from 69 to 110 MB)
 #ifndef RT_SPH_PARK_DEN
 #define RT_SPH_PARK_DEN 2
 #endif
 constexpr int kSphParkDen = RT_SPH_PARK_DEN;
-// RT_SPH_SEL: every lane runs both halves of a step (box test and
-// discriminant) and keeps its entry's by selects; RT_SPH_CHK: steps between
-// two checks of the parking condition (a lane that parks in between holds
-// still).  Round 6, config 4 (Msamples/s): every step 3,512-3,520; selects
-// 3,059 (selects + every 2 / 3 steps 3,112 / 3,127); branch-form steps checked
-// every 2 / 3 / 4 / 5 / 6 / 8 / 12 steps 3,738 / 3,811 / 3,832 / 3,845 / 3,868 /
-// 3,829 / 3,791, every 6 or 8 with the roots at 1/3 3,885 / 3,893
-// (profiles/r6/ab_results.md)
-#ifndef RT_SPH_SEL
-#define RT_SPH_SEL 0
-#endif
-#ifndef RT_SPH_CHK
-#define RT_SPH_CHK 6
-#endif
-// One step of a lane's compact sphere-BVH walk in select form (RT_SPH_SEL).
-__device__ __forceinline__ void sphere_step_sel(const uint4* __restrict__ ent, uint32_t& idx, uint32_t& leaf,
-                                                float& pb, float& pdisc, const RayBox& rb, f3 o, f3 d,
-                                                float a, float tmin, float best) {
-    const uint4 e = ent[idx];
-    const bool inner = (e.w & 0x80000000u) != 0u;
-    const bool h = lds_node_hit_nf(e, rb, tmin, best);
-    const f3 oc = o - f3{__uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z)};
-    const float bq = 2.0f * dot(oc, d);
-    const float cc = dot(oc, oc) - __uint_as_float(e.w);
-    const float disc = bq * bq - (4.0f * a) * cc;
-    const bool park = !inner && disc > 0.0f;  // sph_test up to the discriminant (shaders_old.metal:108-136)
-    leaf = park ? idx : leaf;
-    pb = park ? bq : pb;
-    pdisc = park ? disc : pdisc;
-    idx = (inner && !h) ? (e.w & 0x7FFFFFFFu) : idx + 1;
-}
-// The same step with the kernel's branches (the shipped form).
-__device__ __forceinline__ void sphere_step_br(const uint4* __restrict__ ent, uint32_t& idx, uint32_t& leaf,
-                                               float& pb, float& pdisc, const RayBox& rb, f3 o, f3 d,
-                                               float a, float tmin, float best) {
-    const uint4 e = ent[idx];
-    if (e.w & 0x80000000u) {
-        idx = lds_node_hit_nf(e, rb, tmin, best) ? idx + 1 : (e.w & 0x7FFFFFFFu);
-    } else {  // sph_test up to the discriminant (shaders_old.metal:108-136)
-        const f3 oc = o - f3{__uint_as_float(e.x), __uint_as_float(e.y), __uint_as_float(e.z)};
-        const float bq = 2.0f * dot(oc, d);
-        const float cc = dot(oc, oc) - __uint_as_float(e.w);
-        const float disc = bq * bq - (4.0f * a) * cc;
-        if (disc > 0.0f) {
-            leaf = idx;
-            pb = bq;
-            pdisc = disc;
-        }
-        idx = idx + 1;  // a leaf's escape is the next entry
-    }
-}
-template <bool ANY>
-__device__ __forceinline__ void sphere_walk(const uint4* __restrict__ ent, const uint16_t* __restrict__ ids,
-                                            uint32_t nN, uint32_t nT, f3 o, f3 d, float tmin, float& best,
-                                            int& id) {
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
-    const float a = dot(d, d);
-    const RayBox rb = ray_box(o, d);
-    // entry range of this lane's walk over the concatenated layouts
-    uint32_t idx = octant(d) * nN;
-    const uint32_t end = idx + nN;
-    if (ANY && id >= 0) idx = end;
-    uint32_t leaf = kNone;                      // the parked leaf
-    float pb = 0.0f, pdisc = 0.0f;              // its b and discriminant
-    [[maybe_unused]] constexpr int ST = ANY ? 24 : 16;
-    RT_STAT(ST, 1);
-    RT_STAT(ST + 1, __popcll(__ballot(1)));
-    for (;;) {
-        for (;;) {  // cheap steps until the lane parks a leaf or leaves its range
-            const bool adv = idx < end && leaf == kNone;
-            if (__builtin_amdgcn_ballot_w64(adv) == 0) break;
-            RT_STAT(ST + 2, 1);
-            RT_STAT(ST + 3, __popcll(__builtin_amdgcn_ballot_w64(adv)));
-#if RT_SPH_SEL
-            if (adv) sphere_step_sel(ent, idx, leaf, pb, pdisc, rb, o, d, a, tmin, best);
-            if (false) {
-#else
-            if (adv) {
-#endif
-                const uint4 e = ent[idx];
-                if (e.w & 0x80000000u) {
-                    idx = lds_node_hit_nf(e, rb, tmin, best) ? idx + 1 : (e.w & 0x7FFFFFFFu);
-                } else {  // sph_test up to the discriminant (shaders_old.metal:108-136)
-                    const f3 oc = o - f3{__uint_as_float(e.x), __uint_as_float(e.y),
-                                         __uint_as_float(e.z)};
-                    const float bq = 2.0f * dot(oc, d);
-                    const float cc = dot(oc, oc) - __uint_as_float(e.w);
-                    const float disc = bq * bq - (4.0f * a) * cc;
-                    if (disc > 0.0f) {
-                        leaf = idx;
-                        pb = bq;
-                        pdisc = disc;
-                    }
-                    idx = idx + 1;  // a leaf's escape is the next entry
-                }
-            }
-#if RT_SPH_CHK > 1
-#pragma unroll
-            for (int q = 1; q < RT_SPH_CHK; ++q) {  // more steps before the next check
-                RT_STAT(ST + 2, 1);
-                RT_STAT(ST + 3, __popcll(__builtin_amdgcn_ballot_w64(idx < end && leaf == kNone)));
-                if (idx < end && leaf == kNone) {
-                    if (RT_SPH_SEL)
-                        sphere_step_sel(ent, idx, leaf, pb, pdisc, rb, o, d, a, tmin, best);
-                    else
-                        sphere_step_br(ent, idx, leaf, pb, pdisc, rb, o, d, a, tmin, best);
-                }
-            }
-#endif
-            const int parked = __popcll(__builtin_amdgcn_ballot_w64(leaf != kNone));
-            const int live = __popcll(__builtin_amdgcn_ballot_w64(idx < end || leaf != kNone));
-            if (kSphParkDen * parked >= live) break;
-        }
-        if (__builtin_amdgcn_ballot_w64(leaf != kNone) == 0) break;
-        RT_STAT(ST + 5, 1);
-        RT_STAT(ST + 6, __popcll(__builtin_amdgcn_ballot_w64(leaf != kNone)));
-        if (leaf != kNone) {  // the roots of the parked leaves (sph_test)
-            const float sq = sqrtf(pdisc);
-            const float a2 = 2.0f * a;
-            float t = (-pb - sq) / a2;
-            if (!(t > tmin)) t = (-pb + sq) / a2;
-            if (ANY) {
-                if (t > tmin && t < best) {
-                    id = 0;
-                    idx = end;
-                }
-            } else if (t > tmin && t < 3.0e38f && t <= best) {
-                const int s = (int)(nT + ids[leaf]);
-                if (t < best || s < id) {
-                    best = t;
-                    id = s;
-                }
-            }
-            leaf = kNone;
-        }
-    }
-}
 
 // Per-lane walk of the sphere BVH with LEAF BOXES (rt_scene.cpp
-// build_sphere_box; RT_SPH_LEAFBOX): every entry is a near/far fp16 box -- a
-// leaf's box is its padded sphere box, like any node's -- so every step of
-// every lane is the same select-form box test (the compact walk above runs
-// the box test and the discriminant side by side whenever a wave holds lanes
-// at both kinds of entry, ~33 VALU a step).  A lane whose leaf box is hit
-// parks the leaf; the parked lanes' spheres are tested with sph_test (the
-// discriminant, then the IEEE roots) once they are >= 1/kSphBoxParkDen of the
-// walkers, checked every kSphBoxChk steps.  Candidates are ranked by
-// (t, sphere id) as in every walk: the brute-force answer.
+// build_sphere_box), the walk of the sphere kernel: every entry is a near/far
+// fp16 box -- a leaf's box is its padded sphere box, like any node's -- so
+// every step of every lane is the same select-form box test (a lockstep walk
+// of the compact entries ran the box test and the discriminant side by side
+// whenever a wave held lanes at both kinds of entry, ~33 VALU a step; DESIGN.md
+// §5).  After Aila & Laine's postponed leaf processing,
+// in stackless form: a lane whose leaf box is hit parks the leaf; the parked
+// lanes' spheres are tested with sph_test (the discriminant, then the IEEE
+// roots) once they are >= 1/RT_SPH_BOX_PARK_DEN of the walkers, checked every
+// RT_SPH_BOX_CHK steps (a lane that parks in between holds still).  Per lane
+// the entries are visited in the same order whatever the other lanes do, and
+// candidates are ranked by (t, sphere id) as in every walk:
+// the brute-force answer.  ANY: id becomes >= 0 on the first accepted hit
+// (and that lane stops).
 // Config 4 (Msamples/s, profiles/r6/ab_results.md): the compact walk checked
 // every step 3,512-3,520, every 6 steps 3,867-3,874; leaf boxes checked every
 // 2 / 4 / 5 / 6 / 8 steps 3,883 / 4,018 / 4,027 / 4,042-4,044 / 4,037 with the
 // roots at 1/3 (1/2 and 1/4 at every 6: 3,989 / 4,038); leaves of 2 / 3 / 4
 // spheres 3,883 / 3,734 / 3,591
-#ifndef RT_SPH_LEAFBOX
-#define RT_SPH_LEAFBOX 1
-#endif
 #ifndef RT_SPH_BOX_PARK_DEN
 #define RT_SPH_BOX_PARK_DEN 3
 #endif
@@ -543,7 +412,7 @@ __device__ __forceinline__ void sphere_walk_box(const uint4* __restrict__ ent, c
             for (int q = 0; q < RT_SPH_BOX_CHK; ++q) {
                 RT_STAT(ST + 2, 1);
                 RT_STAT(ST + 3, __popcll(__builtin_amdgcn_ballot_w64(idx < end && leaf == kNone)));
-                if (idx < end && leaf == kNone) {
+                if (idx < end && leaf == kNone) {  // cbvh_step, spelled out: the call compiles to other code here
                     const uint4 e = ent[idx];
                     const bool inner = (e.w & 0x80000000u) != 0u;
                     const bool h = lds_node_hit_nf(e, rb, tmin, best);
@@ -670,8 +539,8 @@ __device__ __forceinline__ bool tri_cbvh_any_packet(const uint4* __restrict__ cn
     return found;
 }
 
-// Per-lane compact-BVH walks with POSTPONED LEAVES (as sphere_walk parks its
-// roots): a lane whose box test passes at a leaf parks the leaf and
+// Per-lane compact-BVH walks with POSTPONED LEAVES (as sphere_walk_box parks
+// its leaves): a lane whose box test passes at a leaf parks the leaf and
 // stops; the others walk on until at least 1/kTriParkDen of the lanes
 // still walking are parked, then the wave runs the triangle tests of all
 // parked lanes together -- instead of every mixed step paying for the box
@@ -685,21 +554,15 @@ __device__ __forceinline__ bool tri_cbvh_any_packet(const uint4* __restrict__ cn
 #define RT_TRI_PARK_DEN 4
 #endif
 constexpr int kTriParkDen = RT_TRI_PARK_DEN;
-// RT_TRI_LOOKAHEAD: the next sequential entry requested one step early
-// (100k triangles 888 -> 787 Msamples/s: 4 more VGPRs, 20 spilled; off)
-#ifndef RT_TRI_LOOKAHEAD
-#define RT_TRI_LOOKAHEAD 0
-#endif
-// RT_TRI_SEL: the step's outcome by selects (no exec-mask branches around the
-// box test); RT_TRI_CHK: steps between two checks of the parking condition
+// The step's outcome comes by selects (cbvh_step: no exec-mask branches around
+// the box test); RT_TRI_CHK: steps between two checks of the parking condition
 // (the two ballots, popcounts and compares of the check are a third of a
 // step's instructions; a lane that parks in between holds still).  Round 6,
 // 100k triangles (Msamples/s): branch form, check every step 988-990;
 // selects 1,029; check every 2 steps 1,068; both: every 2 / 3 / 4 / 6 / 8
-// steps 1,082-1,093 / 1,103 / 1,111 / 1,109 / 1,086 (profiles/r6/ab_results.md)
-#ifndef RT_TRI_SEL
-#define RT_TRI_SEL 1
-#endif
+// steps 1,082-1,093 / 1,103 / 1,111 / 1,109 / 1,086 (profiles/r6/ab_results.md).
+// The next sequential entry requested one step early: 888 -> 787 (4 more
+// VGPRs, 20 spilled).
 #ifndef RT_TRI_CHK
 #define RT_TRI_CHK 4
 #endif
@@ -709,81 +572,27 @@ __device__ __forceinline__ void tri_cbvh_walk(const uint4* __restrict__ cn, cons
                                               float tmin, float& best, int& id) {
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     const RayBox rb = ray_box(o, d);
-#if RT_TRI_ONE_LAYOUT  // experiment: every lane in the octant-0 layout (min/max box test)
-    uint32_t idx = 0;
-#else
     uint32_t idx = octant(d) * nN;
-#endif
     const uint32_t end = idx + nN;
     if (ANY && id >= 0) idx = end;
     uint32_t leaf = kNone;
-    [[maybe_unused]] constexpr int ST = ANY ? 24 : 16;  // the sphere_walk slots (no spheres here)
+    [[maybe_unused]] constexpr int ST = ANY ? 24 : 16;  // the slots of sphere_walk_box (no spheres here)
     RT_STAT(ST, 1);
     RT_STAT(ST + 1, __popcll(__ballot(1)));
-#if RT_TRI_LOOKAHEAD
-    // one entry of lookahead: `seq` is the entry after the current one, loaded
-    // one step early, so a step that goes on to idx + 1 (a box hit, or a
-    // missed leaf) finds its entry already requested
-    const uint32_t last = end - 1u;
-    uint4 cur = cn[idx < last ? idx : last];
-    uint4 seq = cn[idx + 1u < last ? idx + 1u : last];
-#endif
     for (;;) {
         for (;;) {
             const bool adv = idx < end && leaf == kNone;
             if (__builtin_amdgcn_ballot_w64(adv) == 0) break;
             RT_STAT(ST + 2, 1);
             RT_STAT(ST + 3, __popcll(__builtin_amdgcn_ballot_w64(adv)));
-            if (adv) {
-#if RT_TRI_LOOKAHEAD
-                const uint4 e = cur;
-                const bool inner = (e.w & 0x80000000u) != 0u;
-                const bool h = lds_node_hit_nf(e, rb, tmin, best);
-                if (h && !inner) leaf = e.w;
-                if (h || !inner) {
-                    idx = idx + 1u;
-                    cur = seq;
-                } else {
-                    idx = e.w & 0x7FFFFFFFu;
-                    cur = cn[idx < last ? idx : last];
-                }
-                seq = cn[idx + 1u < last ? idx + 1u : last];
-#elif RT_TRI_SEL
-                const uint4 e = cn[idx];
-                const bool inner = (e.w & 0x80000000u) != 0u;
-                const bool h = lds_node_hit_nf(e, rb, tmin, best);
-                leaf = (h && !inner) ? e.w : leaf;
-                idx = (h || !inner) ? idx + 1 : (e.w & 0x7FFFFFFFu);
-#else
-                const uint4 e = cn[idx];
-                const bool inner = (e.w & 0x80000000u) != 0u;
-#if RT_TRI_ONE_LAYOUT
-                if (!lds_node_hit(e, rb, tmin, best)) {
-#else
-                if (!lds_node_hit_nf(e, rb, tmin, best)) {
-#endif
-                    idx = inner ? (e.w & 0x7FFFFFFFu) : idx + 1;
-                } else {
-                    if (!inner) leaf = e.w;
-                    idx = idx + 1;
-                }
-#endif
-            }
-#if RT_TRI_CHK > 1
+            if (adv) cbvh_step(cn, idx, leaf, rb, tmin, best);
             // more steps before the next check (a parked lane holds still)
 #pragma unroll
             for (int q = 1; q < RT_TRI_CHK; ++q) {
                 RT_STAT(ST + 2, 1);
                 RT_STAT(ST + 3, __popcll(__builtin_amdgcn_ballot_w64(idx < end && leaf == kNone)));
-                if (idx < end && leaf == kNone) {
-                    const uint4 e = cn[idx];
-                    const bool inner = (e.w & 0x80000000u) != 0u;
-                    const bool h = lds_node_hit_nf(e, rb, tmin, best);
-                    leaf = (h && !inner) ? e.w : leaf;
-                    idx = (h || !inner) ? idx + 1 : (e.w & 0x7FFFFFFFu);
-                }
+                if (idx < end && leaf == kNone) cbvh_step(cn, idx, leaf, rb, tmin, best);
             }
-#endif
             const int parked = __popcll(__builtin_amdgcn_ballot_w64(leaf != kNone));
             const int live = __popcll(__builtin_amdgcn_ballot_w64(idx < end || leaf != kNone));
             if (kTriParkDen * parked >= live) break;
@@ -932,9 +741,6 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
     return mask;
 }
 
-#ifndef RT_PAIR_SEL
-#define RT_PAIR_SEL 0
-#endif
 // Exact pair test (the same arithmetic as the brute-force loops) with the
 // hit ranked lexicographically by (t, triangle id): pairs are visited out of
 // id order here, and (t, id) order is what the id-ordered scan with strict
@@ -946,18 +752,6 @@ __device__ __forceinline__ void pair_test_rank(const float4* r, uint32_t k, f3 o
     const PairDots q = pair_dots(r0, r1, r2, r3, r4, o, d);
     const bool pa = bary_ok(q.denA, q.a1, q.a2);
     const bool pb = bary_ok(q.denB, q.b1, q.b2);
-#if RT_PAIR_SEL  // A/B: the first division by every lane, kept by selects (no exec branch)
-    {
-        const f3 nsel = pa ? f3{r2.y, r2.z, r2.w} : f3{r3.w, r4.x, r4.y};
-        const float t = pair_t(nsel, q.tv, pa ? q.denA : q.denB);
-        const int ia = (int)(pa ? 2 * k : 2 * k + 1);
-        const bool take = (pa || pb) && t > tmin && (t < *best || (!ANY && t == *best && ia < *id));
-        if (!ANY) *best = take ? t : *best;
-        *id = take ? ia : *id;
-    }
-    if (pa && pb) {
-        {
-#else
     if (pa || pb) {
         const f3 nsel = pa ? f3{r2.y, r2.z, r2.w} : f3{r3.w, r4.x, r4.y};
         const float t = pair_t(nsel, q.tv, pa ? q.denA : q.denB);
@@ -967,7 +761,6 @@ __device__ __forceinline__ void pair_test_rank(const float4* r, uint32_t k, f3 o
             *id = ia;
         }
         if (pa && pb) {
-#endif
             const float t2 = pair_t(f3{r3.w, r4.x, r4.y}, q.tv, q.denB);
             const int ib = (int)(2 * k + 1);
             if (t2 > tmin && (t2 < *best || (!ANY && t2 == *best && ib < *id))) {
@@ -976,31 +769,6 @@ __device__ __forceinline__ void pair_test_rank(const float4* r, uint32_t k, f3 o
             }
         }
     }
-}
-
-#ifndef RT_CLU_HELP
-#define RT_CLU_HELP 0
-#endif
-// Position of the (r+1)-th set bit of a 64-bit mask (r < popcount).
-__device__ __forceinline__ uint32_t select_bit64(uint64_t m, uint32_t r) {
-    uint32_t pos = 0;
-    uint32_t lo = (uint32_t)m;
-    uint32_t c = (uint32_t)__builtin_popcount(lo);
-    if (r >= c) {
-        r -= c;
-        pos = 32;
-        lo = (uint32_t)(m >> 32);
-    }
-#pragma unroll
-    for (uint32_t w = 16; w >= 1; w >>= 1) {
-        c = (uint32_t)__builtin_popcount(lo & ((1u << w) - 1u));
-        if (r >= c) {
-            r -= c;
-            pos += w;
-            lo >>= w;
-        }
-    }
-    return pos;
 }
 
 // Closest hit / any hit over the pair records with box clusters: the
@@ -1022,68 +790,6 @@ __device__ __forceinline__ void cluster_query(const SceneView& sv, f3 o, f3 d, f
     if (ALLOW) cand &= sv.shd_mask;
     RT_STAT(12, 1);
     RT_STAT(15, __popcll(__ballot(1)));
-#if RT_CLU_HELP
-    // A/B variant: candidate-round compaction.  In
-    // every round the lanes of the query with no candidate left help the
-    // lanes with two or more: a helper pulls its owner's ray, best and
-    // candidate mask (ds_bpermute), tests the owner's SECOND candidate while
-    // the owner tests its first, and the owner merges the two (t, id)-ranked
-    // results -- both started from the same (best, id), so their
-    // lexicographic minimum is the result of testing both in any order.
-    const uint32_t me = __lane_id();
-    for (;;) {
-        const bool want = cand != 0u && !(ANY && *id >= 0);
-        if (__builtin_amdgcn_ballot_w64(want) == 0) break;
-        const bool two = want && (cand & (cand - 1u)) != 0u;
-        const uint64_t m2 = __builtin_amdgcn_ballot_w64(two);
-        const uint64_t idle = __builtin_amdgcn_ballot_w64(!want);
-        const uint32_t n2 = (uint32_t)__popcll(m2), ni = (uint32_t)__popcll(idle);
-        uint32_t partner = me;
-        bool helped = false, helping = false;
-        if (two) {
-            const uint32_t q = (uint32_t)__popcll(m2 & ((1ull << me) - 1ull));
-            if (q < ni) {
-                partner = select_bit64(idle, q);
-                helped = true;
-            }
-        } else if (!want) {
-            const uint32_t r = (uint32_t)__popcll(idle & ((1ull << me) - 1ull));
-            if (r < n2) {
-                partner = select_bit64(m2, r);
-                helping = true;
-            }
-        }
-        const f3 po{__shfl(o.x, (int)partner), __shfl(o.y, (int)partner), __shfl(o.z, (int)partner)};
-        const f3 pd{__shfl(d.x, (int)partner), __shfl(d.y, (int)partner), __shfl(d.z, (int)partner)};
-        const uint32_t pc = (uint32_t)__shfl((int)cand, (int)partner);
-        const float ob = __shfl(*best, (int)partner);
-        const int oid = __shfl(*id, (int)partner);
-        float tb = helping ? ob : *best;  // a helper starts from its owner's (best, id)
-        int tid = helping ? oid : *id;
-        RT_STAT(13, 1);
-        RT_STAT(14, __popcll(__ballot(want || helping)));
-        if (want || helping) {
-            const uint32_t k = (uint32_t)__builtin_ctz(helping ? (pc & (pc - 1u)) : cand);
-            pair_test_rank<ANY>(sv.pair + kPairF4 * k, k, helping ? po : o, helping ? pd : d, tmin, &tb, &tid);
-        }
-        const float rb = __shfl(tb, (int)partner);
-        const int rid = __shfl(tid, (int)partner);
-        if (want) {
-            cand &= cand - 1u;
-            *best = tb;
-            *id = tid;
-            if (helped) {
-                cand &= cand - 1u;
-                if (ANY) {
-                    if (rid >= 0) *id = rid;
-                } else if (rb < *best || (rb == *best && rid < *id)) {
-                    *best = rb;
-                    *id = rid;
-                }
-            }
-        }
-    }
-#else
     while (cand != 0u && !(ANY && *id >= 0)) {
         RT_STAT(13, 1);
         RT_STAT(14, __popcll(__ballot(1)));
@@ -1091,7 +797,6 @@ __device__ __forceinline__ void cluster_query(const SceneView& sv, f3 o, f3 d, f
         cand &= cand - 1u;
         pair_test_rank<ANY>(sv.pair + kPairF4 * k, k, o, d, tmin, best, id);
     }
-#endif
 }
 
 // closest hit, accept_any_intersection(false) (raytrace.metal:48-49).
@@ -1183,10 +888,8 @@ __device__ __forceinline__ int closest_hit(const SceneView& sv, f3& o, f3& d, fl
             }
         }
     }
-    if (SPH && GEO == kGeoSphLds && RT_SPH_LEAFBOX)
+    if (SPH && GEO == kGeoSphLds)
         sphere_walk_box<false>(sv.sbox, sv.sph, sv.sph_perm, sv.nSB, sv.nT, o, d, tmin, best, id);
-    else if (SPH && GEO == kGeoSphLds)
-        sphere_walk<false>(sv.sent, sv.sid, sv.nN, sv.nT, o, d, tmin, best, id);
     else if (SPH)
         sphere_closest(sv.node, sv.sph, sv.sph_perm, sv.nN, sv.nT, o, d, tmin, best, id);
     *t_io = best;
@@ -1260,10 +963,7 @@ __device__ __forceinline__ bool any_hit(const SceneView& sv, f3& o, f3& d, float
     if (SPH && GEO == kGeoSphLds) {
         float tm = tmax;
         int id = -1;
-        if (RT_SPH_LEAFBOX)
-            sphere_walk_box<true>(sv.sbox, sv.sph, sv.sph_perm, sv.nSB, sv.nT, o, d, tmin, tm, id);
-        else
-            sphere_walk<true>(sv.sent, sv.sid, sv.nN, sv.nT, o, d, tmin, tm, id);
+        sphere_walk_box<true>(sv.sbox, sv.sph, sv.sph_perm, sv.nSB, sv.nT, o, d, tmin, tm, id);
         return id >= 0;
     }
     if (SPH) return sphere_any(sv.node, sv.sph, sv.nN, o, d, tmin, tmax);
@@ -1327,74 +1027,6 @@ __device__ __forceinline__ FusedHit fused_shadow_closest(const SceneView& sv, f3
                     h.id = (int)(2 * k + 1);
                 }
             }
-        }
-    }
-    return h;
-}
-
-// Dual walk of the triangle BVH (A/B variant RT_TRI_DUAL, round 5): the
-// shadow any-hit of bounce b (from p toward the light sample, A) and the
-// closest hit of bounce b + 1 (from the same p along the next direction, B)
-// are independent, so one loop walks both per lane, loading both rays' next
-// entries before testing either: two dependent-load chains in flight per lane
-// instead of one (the 100k-triangle walks wait on memory, not on issue).
-// Each ray visits the same entries in the same order as tri_cbvh_walk and is
-// ranked the same way: the same results.
-__device__ __forceinline__ FusedHit tri_walk_dual(const SceneView& sv, f3 p, f3 dA, float tmaxA, bool litA, f3 dB) {
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
-    const uint4* __restrict__ cn = sv.tnode;
-    const uint32_t nN = sv.nTN;
-    const RayBox ra = ray_box(p, dA), rb = ray_box(p, dB);
-    uint32_t ia = octant(dA) * nN;
-    const uint32_t ea = ia + nN;
-    if (!litA) ia = ea;
-    uint32_t ib = octant(dB) * nN;
-    const uint32_t eb = ib + nN;
-    uint32_t la = kNone, lb = kNone;
-    FusedHit h{false, -1, 1000.0f};  // max_distance (sampling.metal:155)
-    for (;;) {
-        for (;;) {
-            const bool aa = ia < ea && la == kNone, ab = ib < eb && lb == kNone;
-            if (__builtin_amdgcn_ballot_w64(aa || ab) == 0) break;
-            // both entries requested before either is tested (clamped indices:
-            // a finished ray re-reads an entry of its own layout, unused)
-            const uint4 na = cn[aa ? ia : ea - 1u];
-            const uint4 nb = cn[ab ? ib : eb - 1u];
-            if (aa) {
-                const bool inner = (na.w & 0x80000000u) != 0u;
-                if (!lds_node_hit_nf(na, ra, 0.0f, tmaxA)) {
-                    ia = inner ? (na.w & 0x7FFFFFFFu) : ia + 1;
-                } else {
-                    if (!inner) la = na.w;
-                    ia = ia + 1;
-                }
-            }
-            if (ab) {
-                const bool inner = (nb.w & 0x80000000u) != 0u;
-                if (!lds_node_hit_nf(nb, rb, 0.001f, h.t)) {
-                    ib = inner ? (nb.w & 0x7FFFFFFFu) : ib + 1;
-                } else {
-                    if (!inner) lb = nb.w;
-                    ib = ib + 1;
-                }
-            }
-            const int parked = __popcll(__builtin_amdgcn_ballot_w64(la != kNone)) +
-                               __popcll(__builtin_amdgcn_ballot_w64(lb != kNone));
-            const int live = __popcll(__builtin_amdgcn_ballot_w64(ia < ea || la != kNone)) +
-                             __popcll(__builtin_amdgcn_ballot_w64(ib < eb || lb != kNone));
-            if (kTriParkDen * parked >= live) break;
-        }
-        if (__builtin_amdgcn_ballot_w64(la != kNone || lb != kNone) == 0) break;
-        if (la != kNone) {
-            if (tri_leaf_any(sv.tsorted, la, p, dA, 0.0f, tmaxA)) {
-                h.occluded = true;
-                ia = ea;
-            }
-            la = kNone;
-        }
-        if (lb != kNone) {
-            tri_leaf_closest(sv.tsorted, sv.tperm, lb, p, dB, 0.001f, h.t, h.id);
-            lb = kNone;
         }
     }
     return h;

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B variant with every TU rebuilt (needed when a switch changes the host
-# side too, e.g. RT_SPH_POOL / RT_SPH_LAYOUTS change the scene builder and
-# the LDS size):  tools/ab_full.sh <name> [-Dflags...] -> abvar/librtpt_<name>.so
+# side too, e.g. the scene builder or the LDS size, as RT_LDS_UNDERSIZE
+# does):  tools/ab_full.sh <name> [-Dflags...] -> abvar/librtpt_<name>.so
 set -eu
 N=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)

@@ -2,7 +2,7 @@
 """Per-lane BVH walk counters of a -DRT_STATS build (RTPT_LIB=abvar/librtpt_stats.so)
 on the config-4 scene, or on the random-triangle scene with a 5th argument:
   tools/sphere_stats.py [W H SPP [N [triangles]]]
-(sphere_walk and tri_cbvh_walk share the slots; a triangle scene has no spheres)"""
+(sphere_walk_box and tri_cbvh_walk share the slots; a triangle scene has no spheres)"""
 import ctypes
 import json
 import os
@@ -24,7 +24,7 @@ with Renderer(scene, options=Options.from_env()) as r:
 samples = W * H * SPP
 out = {}
 for name, b in (("closest", 16), ("any", 24)):
-    walks, lanes, steps, step_lanes, leaf_lanes, rounds, parked = st[b:b + 7]
+    walks, lanes, steps, step_lanes, _unused, rounds, parked = st[b:b + 7]  # slot +4 has no writer
     out[name] = {
         "walks_per_sample": walks * 64 / samples,
         "lanes_per_walk": lanes / max(walks, 1),
@@ -32,7 +32,6 @@ for name, b in (("closest", 16), ("any", 24)):
         "step_lane_util": step_lanes / max(64 * steps, 1),
         "lane_steps_per_lane_walk": step_lanes / max(lanes, 1),
         "root_rounds_per_walk": rounds / max(walks, 1),
-        "split_rounds_per_walk": leaf_lanes / max(walks, 1),  # slot +4: split rounds (RT_SPH_SPLIT)
         "parked_per_round": parked / max(rounds, 1),
         "roots_per_lane_walk": parked / max(lanes, 1),
     }
