@@ -1295,10 +1295,10 @@ hipError_t read_debug_stats(unsigned long long* out, int n) {
     static const uint32_t zero[4] = {0, 0, 0, 0};  // the three slot counters
     return hipMemcpyToSymbol(HIP_SYMBOL(g_free_dbg), zero, sizeof(zero));
 #elif defined(RT_STATS)
-    if (n > 32) n = 32;
+    if (n > 40) n = 40;
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rt_stats), n * sizeof(unsigned long long));
     if (e != hipSuccess) return e;
-    const unsigned long long zero[32] = {0};
+    const unsigned long long zero[40] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(g_rt_stats), zero, sizeof(zero));
 #else
     (void)out;

@@ -43,6 +43,13 @@ constexpr uint32_t kCluF4 = 7;   // float4 per box cluster (rt_scene.hpp Compile
 #ifndef RT_SHD_CAND
 #define RT_SHD_CAND 1
 #endif
+// Its closest queries of bounce >= 1 test each lane's entry-side candidates
+// first and the exit-side ones only where they can still win against the hit
+// found (rt_cluorder.hpp); 0: one candidate mask per lane in
+// bit order
+#ifndef RT_CLU_ORDER
+#define RT_CLU_ORDER 1
+#endif
 // Layouts of the triangle BVH (rt_scene.cpp build_tri_sah / rt_lbvh.hip,
 // rt_trace.hpp tri_cbvh_*): one per direction octant, 16 B per node.
 constexpr uint32_t kTriCompactLayouts = 8;

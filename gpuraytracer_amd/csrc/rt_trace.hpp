@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "rt_cluorder.hpp"  // vmin / vmax / safe_rcp and the per-lane cluster split
 #include "rt_kernel.hpp"
 
 namespace rt {
@@ -114,13 +115,16 @@ __device__ __forceinline__ bool sph_test(const float4& S, f3 o, f3 d, float a, f
 // hit, 2: shadow any-hit): [4q] pair records visited per wave, [4q+1] records
 // tested, [4q+2] active lanes summed over tested records, [4q+3] division blocks.
 // Box-cluster queries: [12] queries per wave, [13] candidate rounds per wave,
-// [14] lanes summed over rounds, [15] lanes summed over queries.
+// [14] lanes summed over rounds, [15] lanes summed over queries; the same four
+// apart for the closest queries of bounce >= 1 [32..35] and for the shadow
+// queries [36..39], in the order queries, rounds, lanes over rounds, lanes over
+// queries (the camera query's rounds are in [13], [14] only).
 // Per-lane BVH walks (sphere_walk_box, tri_cbvh_walk), base 16 closest / 24
 // any-hit: [+0] walks per wave, [+1] lanes summed over walks, [+2] walk
 // steps, [+3] lanes summed over them, [+4] unused, [+5] leaf rounds, [+6]
 // parked lanes summed over them.
 #ifdef RT_STATS
-__device__ unsigned long long g_rt_stats[32];
+__device__ unsigned long long g_rt_stats[40];
 __device__ __forceinline__ void stat_wave(int slot, unsigned long long v) {
     const unsigned long long m = __ballot(1);
     if ((threadIdx.x & 63u) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(&g_rt_stats[slot], v);
@@ -171,46 +175,11 @@ struct SceneView {
     float* xstash;            // MIS: per-lane primary hit (p, din), SoA in LDS (rt_mis.hip)
 };
 
-// min / max of the culling tests, issued directly.  fminf/fmaxf lower to
-// v_min/v_max_f32 plus a v_max_f32 x,x "canonicalize" of every operand the
-// compiler cannot prove canonical (loads, values through phis: the
-// loop-carried best, the branch-merged slab terms) -- 8 extra VALU per box
-// cluster and 2 per BVH step.  The operands here are results of arithmetic on
-// finite scene data (no signalling NaNs), for which v_min/v_max_f32 return
-// exactly fminf/fmaxf; and these values only decide what is culled, never a
-// result.
-__device__ __forceinline__ float vmin(float a, float b) {
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float vmax(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float vmin3(float a, float b, float c) {
-    float r;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
 // Per-ray data of the slab test.  1/d uses the 1-ulp hardware reciprocal: the
 // node boxes carry the culling margin, so only speed depends on its rounding.
 struct RayBox {
     f3 invd, oinv;
 };
-
-// 1/v clamped to +-1e20 (v = +-0 gives +-1e20): one v_rcp + one v_med3.
-// Feeds only conservative slab tests (speed, not results, depends on it).
-__device__ __forceinline__ float safe_rcp(float v) {
-    return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(v), -1e20f, 1e20f);
-}
 
 __device__ __forceinline__ RayBox ray_box(f3 o, f3 d) {
     RayBox r;
@@ -741,6 +710,34 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
     return mask;
 }
 
+// The same filter (no SEG, no ALLOW) with the candidates split for an ordered
+// closest query (rt_cluorder.hpp): near | far is the mask
+// above; finished, i.e. disjoint and with the far set promoted where nothing
+// is near.
+__device__ __forceinline__ CluSplit cluster_candidates_split(const SceneView& sv, f3 o, f3 d, float tmin,
+                                                             float tmax) {
+    const RayBox rb = ray_box(o, d);
+    const float iv[3] = {rb.invd.x, rb.invd.y, rb.invd.z};
+    const float oi[3] = {rb.oinv.x, rb.oinv.y, rb.oinv.z};
+    CluSplit s = clu_split_init();
+    uint32_t c = 0;
+    for (; c < sv.nC; ++c) {
+        const float4* r = sv.clu + kCluF4 * c;
+        const uint32_t flags = __float_as_uint(r[3].w);
+        if (flags & 16u) break;  // single-face clusters come last (rt_scene.cpp)
+        float en[3], ex[3], ida[3], tlo, thi;
+        clu_slab(r, flags, iv, oi, o, d, tmin, tmax, en, ex, ida, &tlo, &thi);
+        if (!__builtin_amdgcn_ballot_w64(tlo <= thi)) continue;  // no lane meets the box
+        clu_faces_split(r, flags, en, ex, ida, tlo, thi, &s);
+    }
+    for (; c < sv.nC; ++c) {
+        const float4* r = sv.clu + kCluF4 * c;
+        clu_single_split(r, __float_as_uint(r[3].w), iv, oi, o, d, tmin, tmax, &s);
+    }
+    clu_split_finish(&s);
+    return s;
+}
+
 // Exact pair test (the same arithmetic as the brute-force loops) with the
 // hit ranked lexicographically by (t, triangle id): pairs are visited out of
 // id order here, and (t, id) order is what the id-ordered scan with strict
@@ -779,23 +776,57 @@ __device__ __forceinline__ void pair_test_rank(const float4* r, uint32_t k, f3 o
 // hit, and the MIS light queries: closest hits that only matter up to tmax).
 // ALLOW (the bounce-0 shadow query): only the pairs of the
 // wave-uniform mask sv.shd_mask are tested, free pairs included.
-template <bool ANY, bool SEG = ANY, bool ALLOW = false>
+// ORDER (the closest queries of bounce >= 1 in the box-cluster kernel,
+// DESIGN.md §3.18): the candidates come split (rt_cluorder.hpp); the rounds run
+// over each lane's near set, then over its far set where a far candidate can
+// still win against the best found.  Most waves then end after one round,
+// where one lane that met a box's padded slab used to hold the whole wave for
+// the box's exit face and the wall behind it.  (t, id) ranking makes the
+// visiting order free, and a culled pair holds no hit with t <= best.
+template <bool ANY, bool SEG = ANY, bool ALLOW = false, bool ORDER = false>
 __device__ __forceinline__ void cluster_query(const SceneView& sv, f3 o, f3 d, float tmin,
                                               float* best, int* id) {
+    static_assert(!ORDER || (!ANY && !SEG && !ALLOW), "the ordered form is the plain closest query");
+    [[maybe_unused]] constexpr int ST = ANY ? 36 : 32;  // RT_STATS: shadow / closest queries apart
     for (uint32_t free = ALLOW ? (sv.pair_free & sv.shd_mask) : sv.pair_free; free != 0u; free &= free - 1u) {
         const uint32_t k = (uint32_t)__builtin_ctz(free);
         pair_test_rank<ANY>(sv.pair + kPairF4 * k, k, o, d, tmin, best, id);
     }
-    uint32_t cand = cluster_candidates<SEG, ALLOW>(sv, o, d, tmin, *best, ALLOW ? sv.shd_cskip : 0u);
-    if (ALLOW) cand &= sv.shd_mask;
+    uint32_t cand, far = 0u;
+    [[maybe_unused]] float far_lo = 0.0f;
+    if constexpr (ORDER) {
+        const CluSplit s = cluster_candidates_split(sv, o, d, tmin, *best);
+        cand = s.near;
+        far = s.far;
+        far_lo = s.far_lo;
+    } else {
+        cand = cluster_candidates<SEG, ALLOW>(sv, o, d, tmin, *best, ALLOW ? sv.shd_cskip : 0u);
+        if (ALLOW) cand &= sv.shd_mask;
+    }
     RT_STAT(12, 1);
     RT_STAT(15, __popcll(__ballot(1)));
+    RT_STAT(ST, 1);
+    RT_STAT(ST + 3, __popcll(__ballot(1)));
     while (cand != 0u && !(ANY && *id >= 0)) {
         RT_STAT(13, 1);
         RT_STAT(14, __popcll(__ballot(1)));
+        RT_STAT(ST + 1, 1);
+        RT_STAT(ST + 2, __popcll(__ballot(1)));
         const uint32_t k = (uint32_t)__builtin_ctz(cand);
         cand &= cand - 1u;
         pair_test_rank<ANY>(sv.pair + kPairF4 * k, k, o, d, tmin, best, id);
+    }
+    if constexpr (ORDER) {
+        far = clu_far_needed(far_lo, *best) ? far : 0u;
+        while (far != 0u) {
+            RT_STAT(13, 1);
+            RT_STAT(14, __popcll(__ballot(1)));
+            RT_STAT(ST + 1, 1);
+            RT_STAT(ST + 2, __popcll(__ballot(1)));
+            const uint32_t k = (uint32_t)__builtin_ctz(far);
+            far &= far - 1u;
+            pair_test_rank<false>(sv.pair + kPairF4 * k, k, o, d, tmin, best, id);
+        }
     }
 }
 
@@ -822,7 +853,7 @@ __device__ __forceinline__ int closest_hit(const SceneView& sv, f3& o, f3& d, fl
                 pair_test_rank<false>(sv.pair + kPairF4 * k, k, o, d, tmin, &best, &id);
             }
         } else {
-            cluster_query<false>(sv, o, d, tmin, &best, &id);
+            cluster_query<false, false, false, RT_CLU_ORDER != 0>(sv, o, d, tmin, &best, &id);
         }
     } else if (geo_pairs(GEO)) {
         f3 seg_lo, seg_hi;

@@ -16,8 +16,8 @@ W, H, SPP = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 with Renderer(Scene.cornell_box(W, H), options=Options.from_env()) as r:
     r.render(RenderParams(spp=SPP, bounces=3))
     info = r.last_launch()
-    st = (ctypes.c_uint64 * 32)()
-    assert lib.rt_debug_stats(r._ctx, st, 32) == 0, lib.rt_last_error(r._ctx)
+    st = (ctypes.c_uint64 * 40)()
+    assert lib.rt_debug_stats(r._ctx, st, 40) == 0, lib.rt_last_error(r._ctx)
 names = ["camera", "bounce", "shadow"]
 samples = W * H * SPP
 out = {}
@@ -31,6 +31,12 @@ q, rounds, rl, ql = st[12:16]
 out["clusters"] = {"queries_per_wave": q, "rounds_per_query": rounds / max(q, 1),
                    "lanes_per_round": rl / max(rounds, 1), "lanes_per_query": ql / max(q, 1),
                    "candidate_tests_per_sample": rl / samples}
+# the same apart: closest queries of bounce >= 1 (slots 32-35), shadow queries (36-39)
+for name, base in (("clusters_closest_bounce_ge1", 32), ("clusters_shadow", 36)):
+    q, rounds, rl, ql = st[base:base + 4]
+    out[name] = {"queries_per_wave": q, "rounds_per_query": rounds / max(q, 1),
+                 "lanes_per_round": rl / max(rounds, 1), "lanes_per_query": ql / max(q, 1),
+                 "candidate_tests_per_sample": rl / samples}
 # lane-slot accounting (shader-clock cycles per wave, slots 16-25): where a
 # wave's lanes sit idle because their path already ended (miss / light hit at
 # an earlier bounce) vs. the cycles of live lanes
