@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPT_LIB overrides the in-tree library (A/B builds of the kernel).
 library_path = os.environ.get("RTPT_LIB") or os.path.join(_HERE, "librtpt.so")
@@ -198,6 +198,8 @@ SIGNATURES = {
     "rt_debug_camera_candidates": (ctypes.c_int, [ctypes.POINTER(SceneDesc)] + [ctypes.c_int32] * 4 + [_P]),
     "rt_debug_shadow_candidates": (ctypes.c_int, [ctypes.POINTER(SceneDesc)] + [ctypes.c_int32] * 4 +
                                    [_P, ctypes.POINTER(ctypes.c_int32)]),
+    "rt_debug_cluster_kinds": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(ctypes.c_uint32),
+                                              ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 

@@ -1126,6 +1126,20 @@ int rt_debug_shadow_candidates(const rt_scene_desc* d, int32_t x0, int32_t x1, i
     return RT_OK;
 }
 
+int rt_debug_cluster_kinds(const rt_scene_desc* d, uint32_t* flags, uint32_t capacity, uint32_t* n_clusters) {
+    if (!d || !n_clusters || (!flags && capacity) || !d->camera || !d->square_lights)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    rt::CompiledScene s;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0],
+                           d->spheres, d->n_spheres, &s, &err))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    const size_t rec = 4 * rt::kCluF4, nC = s.clusters.size() / rec;
+    *n_clusters = (uint32_t)nC;
+    for (size_t c = 0; c < nC && c < capacity; ++c) memcpy(&flags[c], &s.clusters[c * rec + 15], 4);
+    return RT_OK;
+}
+
 int rt_debug_stats(rt_ctx* c, uint64_t* out, int n) {
     if (!c || !out || n <= 0) return fail(c, RT_ERR_INVALID_ARG, "null argument");
     DeviceGuard g(c->device);

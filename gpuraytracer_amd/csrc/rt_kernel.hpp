@@ -50,6 +50,15 @@ constexpr uint32_t kCluF4 = 7;   // float4 per box cluster (rt_scene.hpp Compile
 #ifndef RT_CLU_ORDER
 #define RT_CLU_ORDER 1
 #endif
+// The cluster filter takes a leaner wave-uniform path for the kinds the scene
+// compiler marks in the record's flag word (rt_cluorder.hpp kCluTurned,
+// kCluInside, kCluOwnLight): a box turned about one world
+// axis forms its two oblique products from two components, a container every
+// lane starts inside gives its exit side alone, and a shade() shadow query
+// passes over the light's own cluster; 0: the one filter for every cluster
+#ifndef RT_CLU_LEAN
+#define RT_CLU_LEAN 1
+#endif
 // Layouts of the triangle BVH (rt_scene.cpp build_tri_sah / rt_lbvh.hip,
 // rt_trace.hpp tri_cbvh_*): one per direction octant, 16 B per node.
 constexpr uint32_t kTriCompactLayouts = 8;

@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "../../include/rtpt.h"
+#include "rt_cluorder.hpp"
 #include "rt_kernel.hpp"
 
 namespace rt {
@@ -1012,6 +1013,39 @@ static void build_clusters(CompiledScene* out, const rt_float3* verts, uint32_t 
                 all_faces |= 1u << best.slot_pair[sl];
             }
         if (nfaces == 1) flags |= 16u;
+        // turned (rt_cluorder.hpp kCluTurned): a box with faces
+        // across exactly one world axis w, whose other two axis vectors, as the
+        // floats the record holds, have a +-0 component w
+        const uint32_t wbits = flags & 7u;
+        if (nfaces > 1 && (wbits == 1u || wbits == 2u || wbits == 4u)) {
+            const int w = wbits == 1u ? 0 : wbits == 2u ? 1 : 2;
+            bool zero = true;
+            for (int a = 0; a < 3; ++a) {
+                const double c[3] = {best.u[a].x, best.u[a].y, best.u[a].z};
+                zero = zero && (a == w || (float)c[w] == 0.0f);
+            }
+            if (zero) flags |= rt::kCluTurned;
+        }
+        // the light's own cluster (kCluOwnLight): one pair of light triangles
+        // whose every vertex has, bit for bit, the y of the points shade() draws
+        // on the light (light_center.y when neither it nor .z is -0, the kernel's
+        // light_plain form).  The bound on |t - dist| of DESIGN.md §3.19 needs
+        // distances below 2396 and no underflow in n.y * (y - p.y): withheld for
+        // a scene extent above 256, and for |y| or a triangle's |n.y| below 2^-20.
+        if (nfaces == 1 && ext <= 256.0) {
+            const uint32_t k = (uint32_t)__builtin_ctz(all_faces);
+            const float ly = out->light.center[1], lz = out->light.center[2];
+            uint32_t by, bz;
+            memcpy(&by, &ly, 4);
+            memcpy(&bz, &lz, 4);
+            const float kTiny = 9.5367431640625e-07f;  // 2^-20
+            bool own = by != 0x80000000u && bz != 0x80000000u && fabsf(ly) >= kTiny;
+            for (uint32_t t = 2 * k; t < 2 * k + 2 && own; ++t) {
+                own = out->tri_shade[t].s[3] != 0.0f && fabsf(out->tri_isect[t].q[10]) >= kTiny;
+                for (int i = 0; i < 3 && own; ++i) own = memcmp(&verts[3 * t + i].y, &ly, 4) == 0;
+            }
+            if (own) flags |= rt::kCluOwnLight;
+        }
         // padding per axis: tol_n, plus the margin if some face lies across it
         double pad[3];
         for (int a = 0; a < 3; ++a) {
@@ -1024,6 +1058,7 @@ static void build_clusters(CompiledScene* out, const rt_float3* verts, uint32_t 
             memcpy(&f, &v, 4);
             return f;
         };
+        bool shrunk = (flags & 8u) != 0u;  // kCluInside: the shrunk box has an inside
         for (int a = 0; a < 3; ++a) {
             const float lo_f = (float)(best.lo[a] - pad[a]), hi_f = (float)(best.hi[a] + pad[a]);
             if (flags & 8u) {
@@ -1044,6 +1079,7 @@ static void build_clusters(CompiledScene* out, const rt_float3* verts, uint32_t 
                 const float M = fmaxf(fabsf(lo_f), fabsf(hi_f));
                 const float in_lo = (float)(best.lo[a] + tol_seg) + kSlack * (fabsf(lo_f) + M);
                 const float in_hi = (float)(best.hi[a] - tol_seg) - kSlack * (fabsf(hi_f) + M);
+                shrunk = shrunk && in_lo < in_hi;
                 cl.push_back(in_lo);
                 cl.push_back(in_hi);
                 cl.push_back(0.0f);
@@ -1057,6 +1093,7 @@ static void build_clusters(CompiledScene* out, const rt_float3* verts, uint32_t 
         cl.push_back((float)(best.hi[0] + pad[0]));
         cl.push_back((float)(best.hi[1] + pad[1]));
         cl.push_back((float)(best.hi[2] + pad[2]));
+        if (shrunk) flags |= rt::kCluInside;
         cl.push_back(bits(flags));
         for (int sl = 0; sl < 6; ++sl)  // pair bit of each face slot (2*axis + side)
             cl.push_back(bits(best.slot_pair[sl] < 0 ? 0u : 1u << best.slot_pair[sl]));
@@ -1070,15 +1107,18 @@ static void build_clusters(CompiledScene* out, const rt_float3* verts, uint32_t 
     }
     // single-face clusters last: the kernel's main cluster loop stops at the
     // first one and a lean loop slab-tests the rest (rt_trace.hpp)
-    std::vector<float> multi, single;
+    // and among them the light's own clusters last: a shadow query of shade()
+    // stops at the first one
+    std::vector<float> multi, single, own;
     const size_t rec = 28;  // floats per cluster record (rt_kernel.hpp kCluF4 = 7 float4)
     for (size_t c = 0; c < cl.size() / rec; ++c) {
         uint32_t flags;
         memcpy(&flags, &cl[c * rec + 15], 4);
-        std::vector<float>& dst = (flags & 16u) ? single : multi;
+        std::vector<float>& dst = (flags & rt::kCluOwnLight) ? own : (flags & 16u) ? single : multi;
         dst.insert(dst.end(), cl.begin() + c * rec, cl.begin() + (c + 1) * rec);
     }
     multi.insert(multi.end(), single.begin(), single.end());
+    multi.insert(multi.end(), own.begin(), own.end());
     out->clusters.swap(multi);
     out->pair_free_mask = free_mask;
 }

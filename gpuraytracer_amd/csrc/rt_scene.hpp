@@ -115,7 +115,9 @@ struct CompiledScene {
     // (m0, m1, m2, m3) (m4, m5, all, 0) (w0, w1, w2, 0): an oriented box (padded
     // extents) whose faces hold consecutive pair records; m_s = bit of the pair
     // on face slot s = 2*axis + side (0: none), all = their union; flags bit a
-    // = axis a is world axis a (+), bit 3 = container, bit 4 = single face;
+    // = axis a is world axis a (+), bit 3 = container, bit 4 = single face,
+    // bits 5-7 = the kinds of DESIGN.md §3.19 (rt_cluorder.hpp kCluTurned,
+    // kCluInside, kCluOwnLight);
     // w_a = face-plane half width factor of axis a.
     std::vector<float> clusters;
     uint32_t pair_free_mask = 0;        // pairs in no cluster (tested by every lane)

@@ -600,7 +600,10 @@ __device__ __forceinline__ void tri_cbvh_walk(const uint4* __restrict__ cn, cons
 // ALLOW (the bounce-0 shadow query): clusters in the wave-uniform set cskip
 // hold no pair of the wave's occluder mask and are skipped before their slab
 // terms are formed, the container check with them.
-template <bool SEG = false, bool ALLOW = false>
+// OWN (RT_CLU_LEAN; the shadow queries of shade(): tmax = dist - 1e-3 to a
+// point drawn on the light): the light's own cluster (kCluOwnLight) is passed
+// over, its pairs' exact test gives t >= tmax.
+template <bool SEG = false, bool ALLOW = false, bool OWN = false>
 __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o, f3 d, float tmin,
                                                        float tmax, uint32_t cskip = 0u) {
     constexpr float kEps = 1.52587890625e-05f;  // 2^-16 relative slack
@@ -639,6 +642,12 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
         const float4 M0 = r[4], M1 = r[5];
         const uint32_t flags = __float_as_uint(H.w);
         if (flags & 16u) break;  // single-face clusters come last (rt_scene.cpp)
+#if RT_CLU_LEAN
+        // the slab of rt_cluorder.hpp: the same terms, and the turned boxes' lean ones
+        const float wf[3] = {W.x, W.y, W.z};
+        float en[3], ex[3], ida[3], tlo, thi;
+        clu_slab(r, flags, iv, oi, o, d, tmin, tmax, en, ex, ida, &tlo, &thi);
+#else
         const float hi[3] = {H.x, H.y, H.z}, wf[3] = {W.x, W.y, W.z};
         float en[3], ex[3], ida[3];
 #pragma unroll
@@ -661,6 +670,7 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
         const float tlo0 = vmax3(en[0], en[1], vmax(en[2], tmin));
         const float thi0 = vmin3(ex[0], ex[1], vmin(ex[2], tmax));
         const float tlo = fmaf(-kEps, fabsf(tlo0), tlo0), thi = fmaf(kEps, fabsf(thi0), thi0);  // kEps*|x| is exact: the same values
+#endif
         if (!__builtin_amdgcn_ballot_w64(tlo <= thi)) continue;  // no lane meets the box
         const uint32_t m[6] = {__float_as_uint(M0.x), __float_as_uint(M0.y), __float_as_uint(M0.z),
                                __float_as_uint(M0.w), __float_as_uint(M1.x), __float_as_uint(M1.y)};
@@ -686,6 +696,9 @@ __device__ __forceinline__ uint32_t cluster_candidates(const SceneView& sv, f3 o
         const float4* r = sv.clu + kCluF4 * c;
         const float4 A0 = r[0], A1 = r[1], A2 = r[2], H = r[3];
         const uint32_t flags = __float_as_uint(H.w);
+#if RT_CLU_LEAN
+        if (OWN && kLeanOwnLight && (flags & kCluOwnLight)) break;  // wave-uniform; these come last (rt_scene.cpp)
+#endif
         const float4 A[3] = {A0, A1, A2};
         const float hi[3] = {H.x, H.y, H.z};
         float tlo0 = tmin, thi0 = tmax;
@@ -725,6 +738,16 @@ __device__ __forceinline__ CluSplit cluster_candidates_split(const SceneView& sv
         const float4* r = sv.clu + kCluF4 * c;
         const uint32_t flags = __float_as_uint(r[3].w);
         if (flags & 16u) break;  // single-face clusters come last (rt_scene.cpp)
+#if RT_CLU_LEAN
+        // a container every lane of the wave starts inside (the room, seen from
+        // a surface in it): the exit side alone; one lane outside its shrunk
+        // box, and the wave takes the full filter
+        if (kLeanExit && (flags & kCluInside) &&
+            __builtin_amdgcn_ballot_w64(!clu_origin_inside(r, o)) == 0) {
+            clu_container_exit(r, iv, oi, tmax, &s);
+            continue;
+        }
+#endif
         float en[3], ex[3], ida[3], tlo, thi;
         clu_slab(r, flags, iv, oi, o, d, tmin, tmax, en, ex, ida, &tlo, &thi);
         if (!__builtin_amdgcn_ballot_w64(tlo <= thi)) continue;  // no lane meets the box
@@ -783,7 +806,8 @@ __device__ __forceinline__ void pair_test_rank(const float4* r, uint32_t k, f3 o
 // where one lane that met a box's padded slab used to hold the whole wave for
 // the box's exit face and the wall behind it.  (t, id) ranking makes the
 // visiting order free, and a culled pair holds no hit with t <= best.
-template <bool ANY, bool SEG = ANY, bool ALLOW = false, bool ORDER = false>
+// OWN: cluster_candidates<.., OWN> (the shadow queries of shade()).
+template <bool ANY, bool SEG = ANY, bool ALLOW = false, bool ORDER = false, bool OWN = false>
 __device__ __forceinline__ void cluster_query(const SceneView& sv, f3 o, f3 d, float tmin,
                                               float* best, int* id) {
     static_assert(!ORDER || (!ANY && !SEG && !ALLOW), "the ordered form is the plain closest query");
@@ -800,7 +824,7 @@ __device__ __forceinline__ void cluster_query(const SceneView& sv, f3 o, f3 d, f
         far = s.far;
         far_lo = s.far_lo;
     } else {
-        cand = cluster_candidates<SEG, ALLOW>(sv, o, d, tmin, *best, ALLOW ? sv.shd_cskip : 0u);
+        cand = cluster_candidates<SEG, ALLOW, OWN>(sv, o, d, tmin, *best, ALLOW ? sv.shd_cskip : 0u);
         if (ALLOW) cand &= sv.shd_mask;
     }
     RT_STAT(12, 1);
@@ -944,7 +968,7 @@ __device__ __forceinline__ bool any_hit(const SceneView& sv, f3& o, f3& d, float
             if (sv.shd_mask == 0u) return false;
             cluster_query<true, true, true>(sv, o, d, tmin, &tm, &id);
         } else {
-            cluster_query<true>(sv, o, d, tmin, &tm, &id);
+            cluster_query<true, true, false, false, RT_CLU_LEAN != 0>(sv, o, d, tmin, &tm, &id);
         }
         if (id >= 0) return true;
     } else if (geo_pairs(GEO)) {

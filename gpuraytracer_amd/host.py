@@ -277,6 +277,16 @@ class Scene:
         _check(lib.rt_scene_describe_ex(ctypes.byref(self.desc()), opt, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in SceneInfo._fields_}
 
+    def cluster_kinds(self) -> list:
+        """The flag word of each box cluster the scene compiles to, in the
+        kernel's order (rt_debug_cluster_kinds): bits 0-2 world axes,
+        8 container, 16 single face, 32 turned about one world axis, 64
+        container with a shrunk box, 128 the light's own cluster."""
+        flags = (ctypes.c_uint32 * 32)()
+        n = ctypes.c_uint32()
+        _check(lib.rt_debug_cluster_kinds(ctypes.byref(self.desc()), flags, 32, ctypes.byref(n)))
+        return [int(flags[c]) for c in range(n.value)]
+
     def desc(self, device: int = 0) -> SceneDesc:
         d = SceneDesc()
         d.camera = ctypes.pointer(self.camera)

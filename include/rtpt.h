@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RTPT_ABI_VERSION 9
+#define RTPT_ABI_VERSION 10
 
 /* Maximum bounce count: Halton dimensions 2+5b..5+5b must stay inside the
  * 24-entry `primes[]` table (`RTrace/sampling.metal:97-104`); b <= 3. */
@@ -409,6 +409,16 @@ int rt_debug_camera_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x
  * it runs the generic query whatever this function reports. */
 int rt_debug_shadow_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x1, int32_t y0, int32_t y1,
                                uint8_t* may_occlude, int32_t* available);
+
+/* Debug (host-only): the flag word of each box cluster the scene compiles to,
+ * in the order the kernel visits them (multi-face clusters, then single-face
+ * ones).  Bits 0-2: box axis a is world axis a; 8: container (world-aligned,
+ * with room inside); 16: single face; and the kinds the filter has a leaner
+ * path for (gpuraytracer_amd/csrc/rt_cluorder.hpp): 32 a box
+ * turned about one world axis, 64 a container with a non-empty shrunk box,
+ * 128 the light's own cluster.  flags: room for capacity words (may be null
+ * when capacity is 0); *n_clusters: how many the scene has (at most 31). */
+int rt_debug_cluster_kinds(const rt_scene_desc* scene, uint32_t* flags, uint32_t capacity, uint32_t* n_clusters);
 
 /* The reference's image epilogue (RTrace/image.swift:35-65): fp16 round trip,
  * ×2 exposure, Reinhard, gamma 1/2.2, clamp, truncating UInt8, alpha 255.
