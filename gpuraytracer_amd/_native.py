@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPT_LIB overrides the in-tree library (A/B builds of the kernel).
 library_path = os.environ.get("RTPT_LIB") or os.path.join(_HERE, "librtpt.so")
@@ -108,6 +108,8 @@ WALKS = {"auto": 0, "lockstep": 1, "free": 2, "sorted": 3}
 
 RT_OK = 0
 RT_OUT_DEVICE, RT_OUT_FP16, RT_OUT_NONE, RT_KEEP_SUM, RT_OUT_RGBA8 = 0x1, 0x2, 0x4, 0x8, 0x10
+RT_RAYS_ANY, RT_RAYS_EXACT = 0x100, 0x200
+RT_RAYS_CHUNK = 2048  # consecutive rays one workgroup of the query kernel traces
 RT_MAX_BOUNCES = 4
 RT_COMM_ID_BYTES = 128
 STATUS = {0: "RT_OK", 1: "RT_ERR_INVALID_ARG", 2: "RT_ERR_NO_DEVICE", 3: "RT_ERR_OUT_OF_MEMORY",
@@ -135,6 +137,22 @@ class TileLayout(ctypes.Structure):  # rt_tile_layout_info
                 ("row_bytes", ctypes.c_uint64), ("tile_bytes", ctypes.c_uint64)]
 
 
+class Ray(ctypes.Structure):  # rt_ray
+    _fields_ = [("origin", ctypes.c_float * 3), ("tmin", ctypes.c_float),
+                ("dir", ctypes.c_float * 3), ("tmax", ctypes.c_float)]
+
+
+class RayHit(ctypes.Structure):  # rt_ray_hit
+    _fields_ = [("t", ctypes.c_float), ("id", ctypes.c_int32)]
+
+
+class RayDomainInfo(ctypes.Structure):  # rt_ray_domain_info
+    _fields_ = [(n, ctypes.c_float) for n in ("origin_max", "dir_len2_min", "dir_len2_max", "tmax_max")]
+
+
+assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 8 and Ray.dir.offset == 16
+
+
 class MisParamsC(ctypes.Structure):  # rt_mis_params
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("camera_rays", "mis_samples", "row_start", "row_step", "row_count", "flags")]
@@ -151,6 +169,9 @@ SIGNATURES = {
     "rt_fill_seeds": (ctypes.c_int, [_P, ctypes.c_uint64]),
     "rt_render": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P]),
     "rt_render_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P]),
+    "rt_trace_rays": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P]),
+    "rt_trace_rays_async": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
+    "rt_debug_ray_domain": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(RayDomainInfo)]),
     "rt_last_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_destroy": (ctypes.c_int, [_P]),
     "rt_last_launch": (ctypes.c_int, [_P, ctypes.POINTER(LaunchInfo)]),

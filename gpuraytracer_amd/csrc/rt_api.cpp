@@ -59,6 +59,10 @@ struct rt_ctx {
     uint32_t mis_tab_S = 0;        // samples per strategy it was built for
     void* d_out8 = nullptr;        // staging for host RGBA8 outputs
     size_t out8_cap = 0;
+    void* d_rays = nullptr;        // staging for host rays and hits (rt_trace_rays)
+    size_t rays_cap = 0;
+    void* d_hits = nullptr;
+    size_t hits_cap = 0;
     void* d_mis_part = nullptr;    // per-ray MIS results of a split launch (rt_mis.hip)
     size_t mis_part_cap = 0;
     uint32_t* d_seeds = nullptr;
@@ -152,6 +156,8 @@ void release(rt_ctx* c) {
     (void)hipFree(c->d_mis_tab);
     (void)hipFree(c->d_out8);
     (void)hipFree(c->d_mis_part);
+    (void)hipFree(c->d_rays);
+    (void)hipFree(c->d_hits);
     (void)hipFree(c->d_seeds);
     (void)hipFree(c->d_sum);
     (void)hipFree(c->d_out);
@@ -601,6 +607,70 @@ int render_mis_impl(rt_ctx* c, const rt_mis_params* p, float* out, uint8_t* out8
     return RT_OK;
 }
 
+// rt_trace_rays / rt_trace_rays_async: one launch of the query kernel
+// (rt_rays.hip) over the context's tables.  Host pointers go through the
+// context's staging buffers on its own stream.
+int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, rt_ray_hit* hits, bool dev,
+                    hipStream_t stream, bool sync) {
+    static_assert(sizeof(rt_ray) == 32 && sizeof(rt_ray_hit) == 8, "rt_ray / rt_ray_hit layout");
+    if (flags & ~(uint32_t)(RT_OUT_DEVICE | RT_RAYS_ANY | RT_RAYS_EXACT))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_trace_rays: unknown flag bits");
+    if (n > 0x80000000ull) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_rays: n > 2^31");
+    if (n == 0) return RT_OK;
+    if (!rays || !hits) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_rays: rays or hits is null");
+    hipError_t e;
+    const void* krays = rays;
+    void* khits = hits;
+    if (!dev) {
+        int st;
+        if ((st = ensure_staging(c, &c->d_rays, &c->rays_cap, (size_t)n * sizeof(rt_ray), "hipMalloc(ray staging)")) != RT_OK ||
+            (st = ensure_staging(c, &c->d_hits, &c->hits_cap, (size_t)n * sizeof(rt_ray_hit), "hipMalloc(hit staging)")) != RT_OK)
+            return st;
+        if ((e = hipMemcpyAsync(c->d_rays, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, stream)) != hipSuccess)
+            return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(rays)", e);
+        krays = c->d_rays;
+        khits = c->d_hits;
+    }
+    rt::RayQueryParams K;
+    memset(&K, 0, sizeof(K));
+    const rt::CompiledScene& s = c->scene;
+    K.tri_isect = c->d_tri_isect;
+    K.pair_isect = c->d_pair_isect;
+    K.sph_isect = c->d_sph_isect;
+    K.sph_nodes = c->d_sph_nodes;
+    K.sph_perm = c->d_sph_perm;
+    K.sph_compact = rt::sphere_compact_usable(s) ? 1u : 0u;
+    K.sph_box = K.sph_compact ? c->d_sph_box : nullptr;
+    K.tri_nodes = c->d_tri_nodes;
+    K.tri_sorted = c->d_tri_sorted;
+    K.tri_perm = c->d_tri_perm;
+    K.clusters = c->d_clusters;
+    K.nT = (uint32_t)s.tri_isect.size();
+    K.nP = (uint32_t)s.pair_isect.size();
+    K.nS = (uint32_t)s.sph_isect.size();
+    K.nN = s.sph_layout_nodes;
+    K.nTN = c->tri_bvh_nodes;
+    K.nC = (uint32_t)(s.clusters.size() / (4 * rt::kCluF4));
+    K.pair_free = s.pair_free_mask;
+    K.rays = reinterpret_cast<const float4*>(krays);
+    K.hits = reinterpret_cast<uint2*>(khits);
+    K.n = (uint32_t)n;
+    K.flags = flags & (RT_RAYS_ANY | RT_RAYS_EXACT);
+    K.dom = rt::ray_domain(s.extent);
+    (void)hipEventRecord(c->ev0, stream);
+    e = rt::launch_ray_query(K, c->scene_mem, stream, &c->launch);
+    if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "ray_query launch", e);
+    c->launched = true;
+    (void)hipEventRecord(c->ev1, stream);
+    c->timed = true;
+    if (!dev && (e = hipMemcpyAsync(hits, khits, (size_t)n * sizeof(rt_ray_hit), hipMemcpyDeviceToHost, stream)) !=
+                    hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(hits)", e);
+    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "ray_query execution", e);
+    return RT_OK;
+}
+
 // rt_create_options (include/rtpt.h) -> the context's choices and the host
 // builds' options.  False (with *why) for a value outside its range.
 struct Resolved {
@@ -861,9 +931,38 @@ int rt_render_async(rt_ctx* c, const rt_render_params* p, void* out_device, void
     return render_impl(c, p, out_device, true, (hipStream_t)hip_stream, false);
 }
 
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, rt_ray_hit* hits) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return trace_rays_impl(c, rays, n, flags, hits, (flags & RT_OUT_DEVICE) != 0, c->stream, true);
+}
+
+int rt_trace_rays_async(rt_ctx* c, const rt_ray* rays_dev, uint64_t n, uint32_t flags, rt_ray_hit* hits_dev,
+                        void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return trace_rays_impl(c, rays_dev, n, flags, hits_dev, true, (hipStream_t)hip_stream, false);
+}
+
+int rt_debug_ray_domain(const rt_scene_desc* d, rt_ray_domain_info* info) {
+    if (!d || !info || !d->camera || !d->square_lights)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    rt::CompiledScene s;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0],
+                           d->spheres, d->n_spheres, &s, &err))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    const rt::RayDomain D = rt::ray_domain(s.extent);
+    info->origin_max = D.origin_max;
+    info->dir_len2_min = D.dir_len2_min;
+    info->dir_len2_max = D.dir_len2_max;
+    info->tmax_max = D.tmax_max;
+    return RT_OK;
+}
+
 int rt_last_kernel_ms(rt_ctx* c, float* ms) {
     if (!c || !ms) return fail(c, RT_ERR_INVALID_ARG, "null argument");
-    if (!c->timed) return fail(c, RT_ERR_STATE, "no render yet");
+    if (!c->timed) return fail(c, RT_ERR_STATE, "no render or ray query yet");
     DeviceGuard g(c->device);
     hipError_t e = hipEventSynchronize(c->ev1);
     if (e == hipSuccess) e = hipEventElapsedTime(ms, c->ev0, c->ev1);

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rt_math.h"
+#include "rt_raydomain.h"
 
 namespace rt {
 
@@ -194,6 +195,52 @@ struct MisParams {
     uint32_t row_start, row_step, row_count;
     float4* part;              // split launches: one float4 per record and pixel, or null (rt_mis.hip SPLIT)
 };
+// ---- batched ray queries (rt_rays.hip; include/rtpt.h rt_trace_rays) --------
+constexpr uint32_t kRaysAny = 0x100u;    // RT_RAYS_ANY
+constexpr uint32_t kRaysExact = 0x200u;  // RT_RAYS_EXACT
+// A workgroup of kBlockThreads lanes stages its layout's records once and
+// traces kRayChunk consecutive rays, 64 consecutive rays per wave and pass
+// (RT_RAYS_CHUNK of include/rtpt.h).
+constexpr uint32_t kRayChunk = 2048;
+// The layout a query takes for the layout choose_kernel gives the context: the
+// free and sorted schedulers are render schedulers, a query runs their scenes
+// through the lockstep walks; the path-sorting pair kernel has no query form.
+constexpr int ray_query_layout(int lay) {
+    return (lay == kLayFreeSph || lay == kLaySortSph)   ? (int)kLaySphLds
+           : (lay == kLayFreeTri || lay == kLaySortTri) ? (int)kLayTriBvh
+           : lay == kLayPairSorted                      ? (int)kLayPairLds
+                                                        : lay;
+}
+// THE dynamic LDS of a query workgroup of layout `lay` (after ray_query_layout):
+// pair or triangle records, then the box clusters; no Halton tables.  The
+// kernel places its arrays by these terms and the launcher requests exactly this.
+__host__ __device__ constexpr size_t ray_query_lds_bytes(int lay, uint32_t nT, uint32_t nP, uint32_t nC) {
+    return lay == kLayTriLds                            ? (size_t)48 * nT
+           : (lay == kLayPairLds || lay == kLaySphLds)  ? (size_t)16 * kPairF4 * nP
+           : lay == kLayPairClu                         ? (size_t)16 * (kPairF4 * nP + kCluF4 * nC)
+                                                        : (size_t)0;
+}
+struct RayQueryParams {
+    const float4* tri_isect;   // the scene tables, as KParams
+    const float4* pair_isect;
+    const float4* sph_isect;
+    const float4* sph_nodes;
+    const uint32_t* sph_perm;
+    const uint4* sph_box;
+    const uint4* tri_nodes;
+    const float4* tri_sorted;
+    const uint32_t* tri_perm;
+    const float4* clusters;
+    uint32_t nT, nP, nS, nN, nTN, nC, pair_free;
+    uint32_t sph_compact;      // every table of the sphere kernel exists (as P.sph_lds != null for a render)
+    const float4* rays;        // 2 float4 per ray: (origin, tmin) (dir, tmax), device memory
+    uint2* hits;               // (t bits, id) per ray, device memory
+    uint32_t n;                // rays, <= 2^31
+    uint32_t flags;            // kRaysAny | kRaysExact
+    RayDomain dom;             // rt_raydomain.h
+};
+hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info);
+
 hipError_t launch_mis(const MisParams& P, SceneMem mem, hipStream_t stream);
 size_t mis_lds_bytes(uint32_t n_tri, uint32_t n_pairs);
 size_t mis_part_bytes(uint32_t camera_rays, size_t pixels);  // 0: no split launch

@@ -1,0 +1,232 @@
+// rt_rays.hip — batched ray queries (include/rtpt.h rt_trace_rays): the exact
+// closest-hit and any-hit queries of the render kernels (rt_trace.hpp
+// closest_hit / any_hit, unchanged) for the caller's own rays, through the
+// record layout and the acceleration structures of the context.
+//
+//   * a workgroup stages its layout's records in LDS once (pair or triangle
+//     records, then the box clusters; no Halton tables) and loops over a
+//     contiguous chunk of kRayChunk rays: a wave reads 64 consecutive rays
+//     (2 KB) per pass, two 16-B loads per lane, and stores 8 B per hit;
+//   * nothing is assumed about the coherence of a wave's rays: closest_hit
+//     without CULL, any_hit without PACKET, no camera or shadow masks;
+//   * rays inside the exactness domain (rt_raydomain.h) take
+//     the accelerated layout.  Its walks decide their leaf rounds by ballots
+//     and its cluster paths branch wave-uniformly, so all 64 lanes stay active
+//     through it: a tail lane past n and a lane whose own ray is outside the
+//     domain run a copy of the wave's first in-domain ray and discard the
+//     result.  Every other ray then takes the id-ordered loop over the global
+//     records (tri_test in id order; the spheres in leaf order, ranked by
+//     (t, id) through sph_perm), which is what RT_RAYS_EXACT asks for every ray;
+//   * the one limit of the accelerated layouts is theirs in the render kernels
+//     too: a ray lying in an oblique triangle's plane to
+//     rounding can be accepted on residues anywhere along the ray, where no
+//     padded box bounds the hit; RT_RAYS_EXACT answers it like the scan;
+//   * no value taken from a ray is used as an index, and the result of a ray
+//     does not depend on the grid shape or on the other rays of its wave.
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdio.h>
+
+#include "rt_kernel.hpp"
+#include "rt_trace.hpp"
+
+namespace rt {
+namespace {
+
+// The id-ordered scan with strict '<'  over the global
+// records: the definition of every answer.  ANY: *id >= 0 on the first
+// accepted hit.  *best enters as the ray's tmax.
+template <bool ANY>
+__device__ __forceinline__ void exact_scan(const RayQueryParams& P, f3 o, f3 d, float tmin, float tmax,
+                                           float* best, int* id) {
+    for (uint32_t k = 0; k < P.nT; ++k) {
+        float t;
+        if (tri_test(P.tri_isect[3 * k], P.tri_isect[3 * k + 1], P.tri_isect[3 * k + 2], o, d, tmin, *best, &t)) {
+            *id = (int)k;
+            if (ANY) return;
+            *best = t;
+        }
+    }
+    const float a = dot(d, d);
+    for (uint32_t k = 0; k < P.nS; ++k) {  // leaf order: ranked by (t, id)
+        float t;
+        if (sph_test(P.sph_isect[k], o, d, a, tmin, tmax, &t)) {
+            if (ANY) {
+                *id = 0;
+                return;
+            }
+            const int sid = (int)(P.nT + P.sph_perm[k]);
+            if (t < *best || (t == *best && sid < *id)) {
+                *best = t;
+                *id = sid;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ float lane_copy(float v, int src) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
+template <int GEO, bool SPH, bool ANY>
+__global__ __launch_bounds__(kBlockThreads) void ray_query_kernel(RayQueryParams P) {
+    constexpr bool kPairs = GEO == kGeoPairLds || GEO == kGeoPairClu || GEO == kGeoSphLds;
+    constexpr bool kStaged = kPairs || GEO == kGeoTriLds;
+    extern __shared__ float4 lds[];
+    SceneView sv;
+    sv.nT = P.nT;
+    sv.nP = P.nP;
+    sv.nS = SPH ? P.nS : 0u;
+    sv.tri = P.tri_isect;
+    sv.pair = P.pair_isect;  // kGeoPairSmem: scalar loads from global memory
+    sv.clu = nullptr;
+    sv.nC = 0u;
+    sv.pair_free = 0u;
+    if constexpr (kStaged) {
+        // ray_query_lds_bytes: the records, then the box clusters
+        const uint32_t ng4 = kPairs ? kPairF4 * P.nP : 3u * P.nT;
+        const float4* src = kPairs ? P.pair_isect : P.tri_isect;
+        for (uint32_t k = threadIdx.x; k < ng4; k += kBlockThreads) lds[k] = src[k];
+        if (GEO == kGeoPairClu)
+            for (uint32_t k = threadIdx.x; k < kCluF4 * P.nC; k += kBlockThreads) lds[ng4 + k] = P.clusters[k];
+        __syncthreads();
+        sv.tri = lds;
+        sv.pair = lds;
+        sv.clu = lds + ng4;
+        sv.nC = P.nC;
+        sv.pair_free = P.pair_free;
+    }
+    sv.tnode = P.tri_nodes;
+    sv.tsorted = P.tri_sorted;
+    sv.tperm = P.tri_perm;
+    sv.nTN = P.nTN;
+    sv.node = P.sph_nodes;
+    sv.sph = P.sph_isect;
+    sv.nN = SPH ? P.nN : 0u;
+    sv.sph_perm = P.sph_perm;
+    sv.sbox = P.sph_box;
+    sv.nSB = P.nN;
+    sv.htab = nullptr;
+    sv.sent = nullptr;
+    sv.sid = nullptr;
+    sv.shade = nullptr;
+    sv.xstash = nullptr;
+
+    const bool accel = (P.flags & kRaysExact) == 0u;
+    const uint64_t base = (uint64_t)blockIdx.x * kRayChunk;
+    for (uint32_t pass = 0; pass < kRayChunk / kBlockThreads; ++pass) {
+        const uint64_t w0 = base + pass * kBlockThreads + (threadIdx.x & ~63u);
+        if (w0 >= P.n) break;  // wave-uniform: nothing left for this wave (no barrier below)
+        const uint64_t i = base + pass * kBlockThreads + threadIdx.x;
+        const bool live = i < P.n;
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+        if (live) {
+            r0 = P.rays[2 * (size_t)i];
+            r1 = P.rays[2 * (size_t)i + 1];
+        }
+        const f3 o{r0.x, r0.y, r0.z}, d{r1.x, r1.y, r1.z};
+        const float tmin = r0.w, tmax = r1.w;
+        const bool in = live && accel && ray_in_domain(P.dom, o, d, tmin, tmax);
+        float best = tmax;
+        int id = -1;
+        const unsigned long long inmask = __builtin_amdgcn_ballot_w64(in);
+        if (inmask != 0ull) {  // wave-uniform
+            const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)inmask) - 1);
+            f3 qo{in ? o.x : lane_copy(o.x, src), in ? o.y : lane_copy(o.y, src), in ? o.z : lane_copy(o.z, src)};
+            f3 qd{in ? d.x : lane_copy(d.x, src), in ? d.y : lane_copy(d.y, src), in ? d.z : lane_copy(d.z, src)};
+            const float qtmin = in ? tmin : lane_copy(tmin, src);
+            const float qtmax = in ? tmax : lane_copy(tmax, src);
+            float qbest = qtmax;
+            int qid = -1;
+            if constexpr (!ANY) {
+                qid = closest_hit<GEO, SPH, /*CULL*/ false>(sv, qo, qd, qtmin, &qbest);
+            } else if constexpr (GEO == kGeoPairClu) {
+                // any_hit's cluster query without the shade()-only rule for the light's own cluster
+                cluster_query<true, true, false, false, false>(sv, qo, qd, qtmin, &qbest, &qid);
+            } else {
+                // the box of [o, o + d*tmax]: tmin >= 0 in the domain, so it bounds every acceptable point
+                const f3 e = qo + qd * qtmax;
+                const f3 lo{fminf(qo.x, e.x), fminf(qo.y, e.y), fminf(qo.z, e.z)};
+                const f3 hi{fmaxf(qo.x, e.x), fmaxf(qo.y, e.y), fmaxf(qo.z, e.z)};
+                qid = any_hit<GEO, SPH, /*PACKET*/ false>(sv, qo, qd, qtmin, qtmax, lo, hi) ? 0 : -1;
+            }
+            if (in) {
+                best = qbest;
+                id = qid;
+            }
+        }
+        if (live && !in) exact_scan<ANY>(P, o, d, tmin, tmax, &best, &id);
+        if (live) {
+            uint2 h;
+            if (ANY) {
+                h.x = 0u;
+                h.y = id >= 0 ? 1u : 0u;
+            } else {
+                h.x = id >= 0 ? __float_as_uint(best) : __float_as_uint(tmax);  // a miss: tmax, bit for bit
+                h.y = (uint32_t)id;
+            }
+            P.hits[(size_t)i] = h;
+        }
+    }
+}
+
+thread_local LaunchInfo g_last_rays;
+
+template <int GEO, bool SPH, bool ANY>
+hipError_t launch_q(const RayQueryParams& P, size_t lds_bytes, hipStream_t stream) {
+    const dim3 grid((uint32_t)(((uint64_t)P.n + kRayChunk - 1) / kRayChunk));
+    LaunchInfo& I = g_last_rays;
+    snprintf(I.kernel, sizeof(I.kernel), "rt::ray_query_kernel<%d, %s, %s>", GEO, SPH ? "true" : "false",
+             ANY ? "true" : "false");
+    I.lanes = 0;
+    I.tables = 0;
+    I.small = 0;
+    I.threads = kBlockThreads;
+    I.grid_x = grid.x;
+    I.grid_y = 1;
+    I.lds = (uint32_t)lds_bytes;
+    hipLaunchKernelGGL((ray_query_kernel<GEO, SPH, ANY>), grid, dim3(kBlockThreads), lds_bytes, stream,
+                       P);  // ray_query_lds_bytes of the layout
+    return hipGetLastError();
+}
+
+template <int GEO, bool SPH>
+hipError_t launch_a(const RayQueryParams& P, size_t lds_bytes, hipStream_t stream) {
+    return (P.flags & kRaysAny) ? launch_q<GEO, SPH, true>(P, lds_bytes, stream)
+                                : launch_q<GEO, SPH, false>(P, lds_bytes, stream);
+}
+
+// The box-cluster layout serves triangle-only scenes, the sphere layout sphere
+// scenes only (choose_kernel); every other layout has both sphere forms.
+template <int GEO>
+hipError_t launch_s(const RayQueryParams& P, size_t lds_bytes, hipStream_t stream) {
+    if constexpr (GEO == kGeoPairClu) return launch_a<GEO, false>(P, lds_bytes, stream);
+    else if constexpr (GEO == kGeoSphLds) return launch_a<GEO, true>(P, lds_bytes, stream);
+    else return P.nS > 0 ? launch_a<GEO, true>(P, lds_bytes, stream) : launch_a<GEO, false>(P, lds_bytes, stream);
+}
+
+}  // namespace
+
+hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info) {
+    if (P.n == 0 || P.n > 0x80000000u) return hipErrorInvalidValue;
+    const KernelChoice kc =
+        choose_kernel(P.nT, P.nP, P.nS, P.nC, P.nTN, P.sph_compact != 0u, 3, mem, kWalkLockstep);
+    const int geo = ray_query_layout(kc.layout);
+    const size_t lds = ray_query_lds_bytes(geo, P.nT, P.nP, P.nC);
+    hipError_t e;
+    switch (geo) {
+        case kGeoTriLds: e = launch_s<kGeoTriLds>(P, lds, stream); break;
+        case kGeoPairLds: e = launch_s<kGeoPairLds>(P, lds, stream); break;
+        case kGeoTriGlobal: e = launch_s<kGeoTriGlobal>(P, lds, stream); break;
+        case kGeoPairSmem: e = launch_s<kGeoPairSmem>(P, lds, stream); break;
+        case kGeoTriBvh: e = launch_s<kGeoTriBvh>(P, lds, stream); break;
+        case kGeoPairClu: e = launch_s<kGeoPairClu>(P, lds, stream); break;
+        case kGeoSphLds: e = launch_s<kGeoSphLds>(P, lds, stream); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (info) *info = g_last_rays;
+    return e;
+}
+
+}  // namespace rt

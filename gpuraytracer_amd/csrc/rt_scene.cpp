@@ -250,7 +250,7 @@ static bool same_bits(const float* a, const float* b, int n) {
 // test at the scene's scale (~1e-6 relative), far below the 1e-3 surface
 // offset of raytrace.metal:67.
 static float culling_margin(const rt_float3* verts, uint32_t n_tri, const SphereGPU* sph = nullptr,
-                            uint32_t n_sph = 0) {
+                            uint32_t n_sph = 0, float rel = 4e-5f) {
     float ext = 2.5f;
     for (uint32_t k = 0; k < 3 * n_tri; ++k)
         ext = fmaxf(ext, fmaxf(fabsf(verts[k].x), fmaxf(fabsf(verts[k].y), fabsf(verts[k].z))));
@@ -258,7 +258,7 @@ static float culling_margin(const rt_float3* verts, uint32_t n_tri, const Sphere
         ext = fmaxf(ext, fmaxf(fabsf(sph[k].center.x), fmaxf(fabsf(sph[k].center.y),
                                                               fabsf(sph[k].center.z))) +
                              fabsf(sph[k].radius));
-    return 4e-5f * ext;
+    return rel * ext;  // rel = 1: the extent itself
 }
 
 // BVH over the spheres (median split of the centroids on the longest axis,
@@ -1198,6 +1198,9 @@ bool compile_scene(const CameraGPU& cam, const MaterialGPU* mats, const rt_float
     const float margin = fmaxf(culling_margin(verts, n_tri, spheres, n_sph),
                                4e-5f * fmaxf(fabsf(cam.position.x),
                                              fmaxf(fabsf(cam.position.y), fabsf(cam.position.z))));
+    // the extent that margin is 4e-5 of: the bound on a query ray's origin
+    out->extent = fmaxf(culling_margin(verts, n_tri, spheres, n_sph, 1.0f),
+                        fmaxf(fabsf(cam.position.x), fmaxf(fabsf(cam.position.y), fabsf(cam.position.z))));
     build_pairs(out, verts, margin);
     build_clusters(out, verts, n_tri, margin,
                    fmax(fabs(cam.position.x), fmax(fabs(cam.position.y), fabs(cam.position.z))));

@@ -123,6 +123,7 @@ struct CompiledScene {
     uint32_t pair_free_mask = 0;        // pairs in no cluster (tested by every lane)
     float tri_lo[3], tri_hi[3];         // bounds of the triangle vertices (BVH build)
     float margin = 0.0f;                // culling margin
+    float extent = 0.0f;                // margin = 4e-5 * extent: scene and camera scale
     MisLightConst mis_light;
     std::vector<MisShade> mis_shade;    // by triangle id
 };

@@ -19,8 +19,9 @@ from dataclasses import dataclass, fields
 import numpy as np
 
 from ._native import (LAYOUTS, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
-                      RT_OUT_NONE, RT_OUT_RGBA8, TRI_BUILDS, WALKS,
-                      BuildStats, CameraGPU, CreateOptions, LaunchInfo, MaterialGPU, MisParamsC, RenderParamsC,
+                      RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, TRI_BUILDS, WALKS,
+                      BuildStats, CameraGPU, CreateOptions, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
+                      RenderParamsC,
                       RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, float3,
                       lib)
 
@@ -287,6 +288,16 @@ class Scene:
         _check(lib.rt_debug_cluster_kinds(ctypes.byref(self.desc()), flags, 32, ctypes.byref(n)))
         return [int(flags[c]) for c in range(n.value)]
 
+    def ray_domain(self) -> dict:
+        """The exactness domain of ``Renderer.trace_rays`` for this scene
+        (rt_debug_ray_domain): ``origin_max``,
+        ``dir_len2_min``, ``dir_len2_max``, ``tmax_max``.  Rays inside it take
+        the accelerated layout, every other ray the id-ordered loop; the
+        answers are the same."""
+        info = RayDomainInfo()
+        _check(lib.rt_debug_ray_domain(ctypes.byref(self.desc()), ctypes.byref(info)))
+        return {k: float(getattr(info, k)) for k, _ in RayDomainInfo._fields_}
+
     def desc(self, device: int = 0) -> SceneDesc:
         d = SceneDesc()
         d.camera = ctypes.pointer(self.camera)
@@ -418,6 +429,49 @@ class Renderer:
                                    ctypes.c_void_p(ptr), ctypes.c_void_p(stream)), self._ctx)
         return out
 
+    def trace_rays(self, rays, any_hit: bool = False, exact: bool = False, out=None, stream=None):
+        """Batched ray queries (rt_trace_rays): ``rays`` is (n, 8) float32,
+        (origin.xyz, tmin, dir.xyz, tmax) per ray.  Closest hit: ``id`` is the
+        primitive (triangles first, then the spheres; -1 for a miss) and ``t``
+        its parameter (a miss: the ray's tmax); ``any_hit``: ``id`` is 1 or 0
+        and ``t`` 0.  ``exact`` sends every ray through the id-ordered loop.
+
+        A numpy array gives ``(t float32[n], id int32[n])`` synchronously.  A
+        torch tensor on the context's device takes the device path and gives
+        torch tensors (views of ``out``, an (n, 2) int32 tensor, when given);
+        with ``stream`` the call is enqueued there without a host sync."""
+        flags = (RT_RAYS_ANY if any_hit else 0) | (RT_RAYS_EXACT if exact else 0)
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, dtype=np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise ValueError("rays must have shape (n, 8)")
+            n = r.shape[0]
+            hits = np.empty((n, 2), np.int32) if out is None else out
+            if hits.dtype != np.int32 or hits.shape != (n, 2) or not hits.flags.c_contiguous:
+                raise ValueError("out must be a contiguous (n, 2) int32 array")
+            _check(lib.rt_trace_rays(self._ctx, r.ctypes.data_as(ctypes.c_void_p), n, flags,
+                                     hits.ctypes.data_as(ctypes.c_void_p)), self._ctx)
+            return hits[:, 0].view(np.float32), hits[:, 1]
+        import torch  # plumbing only: device memory and the caller's stream
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        if not rays.is_cuda or rays.device.index != self.device:
+            raise ValueError("rays must live on the context's device")
+        n = rays.shape[0]
+        hits = torch.empty((n, 2), dtype=torch.int32, device=rays.device) if out is None else out
+        if (hits.dtype != torch.int32 or tuple(hits.shape) != (n, 2) or not hits.is_contiguous()
+                or hits.device != rays.device):
+            raise ValueError("out must be a contiguous (n, 2) int32 tensor on the rays' device")
+        # without a stream: on torch's current stream (after whatever produced
+        # the rays there), then wait for it
+        cur = torch.cuda.current_stream(rays.device) if stream is None else None
+        handle = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        _check(lib.rt_trace_rays_async(self._ctx, ctypes.c_void_p(rays.data_ptr()), n, flags,
+                                       ctypes.c_void_p(hits.data_ptr()), ctypes.c_void_p(handle)), self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        return hits[:, 0].view(torch.float32), hits[:, 1]
+
     def render_progressive(self, params: RenderParams, batch_spp: int, out, stream=None,
                            gather: bool = False):
         """Progressive accumulation: ``params.spp`` samples as
@@ -542,8 +596,8 @@ class Renderer:
         return out
 
     def last_launch(self) -> dict:
-        """The kernel instantiation and launch shape of the last render
-        (rt_last_launch): kernel name as rocprofv3 reports it, lanes per
+        """The kernel instantiation and launch shape of the last render or ray
+        query (rt_last_launch): kernel name as rocprofv3 reports it, lanes per
         pixel, whether the LDS Halton tables were filled, grid, LDS bytes."""
         info = LaunchInfo()
         _check(lib.rt_last_launch(self._ctx, ctypes.byref(info)), self._ctx)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RTPT_ABI_VERSION 10
+#define RTPT_ABI_VERSION 11
 
 /* Maximum bounce count: Halton dimensions 2+5b..5+5b must stay inside the
  * 24-entry `primes[]` table (`RTrace/sampling.metal:97-104`); b <= 3. */
@@ -180,7 +180,7 @@ int rt_render(rt_ctx* ctx, const rt_render_params* params, void* out);
 int rt_render_async(rt_ctx* ctx, const rt_render_params* params, void* out_device,
                     void* hip_stream);
 
-/* Device time of the most recent render kernel (hipEvents on its stream), ms.
+/* Device time of the most recent render or ray-query kernel (hipEvents on its stream), ms.
  * Synchronizes on that event. */
 int rt_last_kernel_ms(rt_ctx* ctx, float* ms);
 
@@ -249,8 +249,8 @@ int rt_place_tiles(rt_ctx* ctx, const void* gathered_device, int32_t world, uint
 int rt_place_tiles_host(const void* gathered, int32_t width, int32_t height, int32_t world,
                         uint32_t flags, void* frame);
 
-/* Which kernel instantiation the most recent rt_render/rt_render_async
- * launched, with its launch shape: lets a caller (bench, tests) state which
+/* Which kernel instantiation the most recent rt_render/rt_render_async or
+ * rt_trace_rays/rt_trace_rays_async launched, with its launch shape: lets a caller (bench, tests) state which
  * configuration it timed or checked.  `kernel` is the demangled name rocprofv3
  * reports, e.g. "rt::path_trace_kernel<3, 6, false, true, 4>". */
 typedef struct rt_launch_info {
@@ -263,6 +263,71 @@ typedef struct rt_launch_info {
     uint32_t lds_bytes;         /* dynamic LDS per workgroup                      */
 } rt_launch_info;
 int rt_last_launch(const rt_ctx* ctx, rt_launch_info* info);
+
+/* ---- batched ray queries -------------------------------------------------
+ * The exact ray queries of the render kernels (DESIGN.md §3.5, §3.6, §3.9,
+ * §3.10, §3.12) for the caller's own rays, through the record layout and the
+ * acceleration structures of the context: picking, visibility and ambient
+ * occlusion between arbitrary points, line of sight, probing a scene.
+ *
+ * Closest hit: id = the lowest-id primitive among those with the smallest
+ * accepted t, tmin < t < tmax strictly; triangles are 0..n_triangles-1, sphere
+ * k of the caller's array is n_triangles + k; t is that primitive's t.  A miss
+ * gives id = -1 and t = the ray's tmax, bit for bit.
+ * RT_RAYS_ANY: id = 1 if any primitive accepts the ray, else 0; t = +0.
+ *
+ * The call is total: any 32 bytes are a ray (NaN, infinity, a zero direction,
+ * tmin >= tmax), and the answer for every ray is what the id-ordered scan with
+ * strict '<' over the primitive tests of DESIGN.md §3.5 / §3.6 gives.  Rays
+ * inside the exactness domain (rt_debug_ray_domain) take the
+ * context's accelerated layout, every other ray takes that scan itself.  The
+ * one known limit of the accelerated layouts: a ray that lies in the plane of
+ * a triangle to rounding (|dot(n, dir)| <= 2^-20 |n| |dir|, n no world axis)
+ * may be accepted by that triangle on rounding residues, anywhere along the
+ * ray; the accelerated answer is then the scan's without that hit.
+ * RT_RAYS_EXACT answers such rays like the scan. */
+typedef struct rt_ray {
+    float origin[3];
+    float tmin;
+    float dir[3];
+    float tmax;
+} rt_ray; /* 32 B */
+
+typedef struct rt_ray_hit {
+    float t;
+    int32_t id;
+} rt_ray_hit; /* 8 B */
+
+#define RT_RAYS_ANY   0x100u /* any-hit (accept_any_intersection) instead of closest hit */
+#define RT_RAYS_EXACT 0x200u /* every ray takes the id-ordered loop (no acceleration)    */
+#define RT_RAYS_CHUNK 2048   /* consecutive rays one workgroup traces                    */
+
+/* Trace n rays and block until done.  flags: RT_RAYS_ANY, RT_RAYS_EXACT, and
+ * RT_OUT_DEVICE when BOTH pointers are device memory (otherwise both are host
+ * memory and the context's staging buffers carry them).  n == 0 is RT_OK
+ * without a launch; n > 2^31, an unknown flag bit, or a null pointer with
+ * n > 0 is RT_ERR_INVALID_ARG.  No seeds are needed.  rt_last_launch then
+ * names the instantiation, e.g. "rt::ray_query_kernel<6, false, false>"
+ * (layout, spheres, any-hit) with its grid, block size and dynamic LDS, and
+ * rt_last_kernel_ms gives the query kernel's device time. */
+int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, uint64_t n, uint32_t flags, rt_ray_hit* hits);
+
+/* Asynchronous variant: both pointers are device memory, the query is enqueued
+ * on `hip_stream` (a hipStream_t, NULL = the null stream).  No host sync. */
+int rt_trace_rays_async(rt_ctx* ctx, const rt_ray* rays_dev, uint64_t n, uint32_t flags,
+                        rt_ray_hit* hits_dev, void* hip_stream);
+
+/* The exactness domain of a scene (host-only, no device): a ray is in it when
+ * all eight floats are finite, max |origin component| <= origin_max,
+ * dir_len2_min <= dot(dir, dir) <= dir_len2_max and
+ * 0 <= tmin < tmax <= tmax_max.  origin_max is the extent every culling
+ * structure's padding was taken from: the largest |coordinate| of the scene
+ * (at least 2.5) or of the camera position, whichever is larger (9.0 for the
+ * Cornell scene).  Only speed depends on it. */
+typedef struct rt_ray_domain_info {
+    float origin_max, dir_len2_min, dir_len2_max, tmax_max;
+} rt_ray_domain_info;
+int rt_debug_ray_domain(const rt_scene_desc* scene, rt_ray_domain_info* info);
 
 /* How rt_create built the scene: which triangle-BVH build ran (rt_tri_bvh_build,
  * 0 = no triangle BVH), its nodes per octant layout, the wall times of the
