@@ -50,6 +50,8 @@ struct rt_ctx {
     float4* d_tri_sorted = nullptr;
     uint32_t* d_tri_perm = nullptr;
     uint32_t tri_bvh_nodes = 0;      // per layout
+    rt::SceneTables tab{};           // what every kernel traces through: set once by rt_create_ex (scene_tables)
+    bool sph_compact = false;        // rt_scene.hpp sphere_compact_usable: the sphere kernel's tables exist
     uint32_t tri_bvh_build_used = 0; // rt_tri_bvh_build of the built tree (0: none)
     float tri_bvh_build_ms = 0.0f;   // wall time of the triangle-BVH build
     size_t tri_bvh_temp_bytes = 0;   // peak temporaries of the GPU SAH build
@@ -132,6 +134,55 @@ hipError_t upload(T** dptr, const void* src, size_t bytes, hipStream_t s) {
     e = hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(s);
+}
+
+// THE scene tables of a compiled scene (rt_kernel.hpp SceneTables): the counts
+// every layout choice is made from, and, with a context, its device tables.
+// nTN: triangle-BVH nodes per layout (0: none).  c == nullptr
+// (rt_scene_describe_ex: no device): the counts alone.
+rt::SceneTables scene_tables(const rt::CompiledScene& s, uint32_t nTN, const rt_ctx* c) {
+    rt::SceneTables t{};
+    t.nT = (uint32_t)s.tri_isect.size();
+    t.nP = (uint32_t)s.pair_isect.size();
+    t.nS = (uint32_t)s.sph_isect.size();
+    t.nN = s.sph_layout_nodes;
+    t.nTN = nTN;
+    t.nC = (uint32_t)(s.clusters.size() / (4 * rt::kCluF4));
+    t.pair_free = s.pair_free_mask;
+    if (!c) return t;
+    t.tri_isect = c->d_tri_isect;
+    t.pair_isect = c->d_pair_isect;
+    t.clusters = c->d_clusters;
+    t.sph_isect = c->d_sph_isect;
+    t.sph_nodes = c->d_sph_nodes;
+    t.sph_perm = c->d_sph_perm;
+    // the leaf-box BVH with the compact entries or not at all (sphere_compact_usable)
+    t.sph_box = rt::sphere_compact_usable(s) ? c->d_sph_box : nullptr;
+    t.tri_nodes = c->d_tri_nodes;
+    t.tri_sorted = c->d_tri_sorted;
+    t.tri_perm = c->d_tri_perm;
+    return t;
+}
+
+// KParams carries the tables as flat members (rt_kernel.hpp).
+void set_tables(rt::KParams* K, const rt::SceneTables& t) {
+    K->tri_isect = t.tri_isect;
+    K->pair_isect = t.pair_isect;
+    K->clusters = t.clusters;
+    K->sph_isect = t.sph_isect;
+    K->sph_nodes = t.sph_nodes;
+    K->sph_perm = t.sph_perm;
+    K->sph_box = t.sph_box;
+    K->tri_nodes = t.tri_nodes;
+    K->tri_sorted = t.tri_sorted;
+    K->tri_perm = t.tri_perm;
+    K->nT = t.nT;
+    K->nP = t.nP;
+    K->nS = t.nS;
+    K->nN = t.nN;
+    K->nTN = t.nTN;
+    K->nC = t.nC;
+    K->pair_free = t.pair_free;
 }
 
 void release(rt_ctx* c) {
@@ -243,33 +294,16 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
 
     rt::KParams K;
     memset(&K, 0, sizeof(K));
-    K.tri_isect = c->d_tri_isect;
+    set_tables(&K, c->tab);
     K.tri_shade = c->d_tri_shade;
-    K.pair_isect = c->d_pair_isect;
-    K.clusters = c->d_clusters;
-    K.nC = (uint32_t)(c->scene.clusters.size() / (4 * rt::kCluF4));
-    K.pair_free = c->scene.pair_free_mask;
-    K.sph_isect = c->d_sph_isect;
     // both compact tables or neither: the launcher takes the sphere kernel when
-    // sph_lds is set, and that kernel's walks read sph_box (rt_scene.hpp)
-    const bool sph_compact = rt::sphere_compact_usable(c->scene);
-    K.sph_lds = sph_compact ? c->d_sph_lds : nullptr;
+    // sph_lds is set, and that kernel's walks read sph_box (scene_tables)
+    K.sph_lds = c->sph_compact ? c->d_sph_lds : nullptr;
     K.sph_lds_id = c->d_sph_lds_id;
-    K.sph_box = (sph_compact && !c->scene.sph_box.empty()) ? c->d_sph_box : nullptr;
     K.sph_shade = c->d_sph_shade;
-    K.sph_nodes = c->d_sph_nodes;
-    K.sph_perm = c->d_sph_perm;
-    K.tri_nodes = c->d_tri_nodes;
-    K.tri_sorted = c->d_tri_sorted;
-    K.tri_perm = c->d_tri_perm;
-    K.nTN = c->tri_bvh_nodes;
     K.seeds = c->d_seeds;
     K.sum = (keep_sum || p->accumulate) ? c->d_sum : nullptr;
     K.out = kout;
-    K.nT = (uint32_t)c->scene.tri_isect.size();
-    K.nS = (uint32_t)c->scene.sph_isect.size();
-    K.nP = (uint32_t)c->scene.pair_isect.size();
-    K.nN = c->scene.sph_layout_nodes;
     K.nE = c->scene.sph_lds_entries;
     const rt::CamConst& cam = c->scene.cam;
     memcpy(K.cam_pos, cam.pos, sizeof(K.cam_pos));
@@ -538,21 +572,11 @@ int render_mis_impl(rt_ctx* c, const rt_mis_params* p, float* out, uint8_t* out8
 
     rt::MisParams K;
     memset(&K, 0, sizeof(K));
-    K.tri_isect = c->d_tri_isect;
-    K.clusters = c->d_clusters;
-    K.nC = (uint32_t)(c->scene.clusters.size() / (4 * rt::kCluF4));
-    K.pair_free = c->scene.pair_free_mask;
-    K.pair_isect = c->d_pair_isect;
+    K.tab = c->tab;  // no spheres (checked above): its sphere members are null / 0
     K.mis_shade = c->d_mis_shade;
     K.u_tab = c->d_mis_tab;
-    K.tri_nodes = c->d_tri_nodes;
-    K.tri_sorted = c->d_tri_sorted;
-    K.tri_perm = c->d_tri_perm;
-    K.nTN = c->tri_bvh_nodes;
     K.out = kout;
     K.out8 = kout8;
-    K.nT = (uint32_t)c->scene.tri_isect.size();
-    K.nP = (uint32_t)c->scene.pair_isect.size();
     const rt::CamConst& cam = c->scene.cam;
     memcpy(K.cam_pos, cam.pos, sizeof(K.cam_pos));
     memcpy(K.cam_u, cam.u, sizeof(K.cam_u));
@@ -633,30 +657,13 @@ int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, r
     }
     rt::RayQueryParams K;
     memset(&K, 0, sizeof(K));
-    const rt::CompiledScene& s = c->scene;
-    K.tri_isect = c->d_tri_isect;
-    K.pair_isect = c->d_pair_isect;
-    K.sph_isect = c->d_sph_isect;
-    K.sph_nodes = c->d_sph_nodes;
-    K.sph_perm = c->d_sph_perm;
-    K.sph_compact = rt::sphere_compact_usable(s) ? 1u : 0u;
-    K.sph_box = K.sph_compact ? c->d_sph_box : nullptr;
-    K.tri_nodes = c->d_tri_nodes;
-    K.tri_sorted = c->d_tri_sorted;
-    K.tri_perm = c->d_tri_perm;
-    K.clusters = c->d_clusters;
-    K.nT = (uint32_t)s.tri_isect.size();
-    K.nP = (uint32_t)s.pair_isect.size();
-    K.nS = (uint32_t)s.sph_isect.size();
-    K.nN = s.sph_layout_nodes;
-    K.nTN = c->tri_bvh_nodes;
-    K.nC = (uint32_t)(s.clusters.size() / (4 * rt::kCluF4));
-    K.pair_free = s.pair_free_mask;
+    K.tab = c->tab;
+    K.sph_compact = c->sph_compact ? 1u : 0u;
     K.rays = reinterpret_cast<const float4*>(krays);
     K.hits = reinterpret_cast<uint2*>(khits);
     K.n = (uint32_t)n;
     K.flags = flags & (RT_RAYS_ANY | RT_RAYS_EXACT);
-    K.dom = rt::ray_domain(s.extent);
+    K.dom = rt::ray_domain(c->scene.extent);
     (void)hipEventRecord(c->ev0, stream);
     e = rt::launch_ray_query(K, c->scene_mem, stream, &c->launch);
     if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "ray_query launch", e);
@@ -885,6 +892,8 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
         delete c;
         return fail(nullptr, status, msg);
     }
+    c->sph_compact = rt::sphere_compact_usable(c->scene);
+    c->tab = scene_tables(c->scene, c->tri_bvh_nodes, c);
     *out_ctx = c;
     return RT_OK;
 }
@@ -1128,12 +1137,13 @@ int rt_scene_describe_ex(const rt_scene_desc* d, const rt_create_options* opt, r
     if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles,
                            d->square_lights[0], d->spheres, d->n_spheres, &s, &err, ro.build))
         return fail(nullptr, RT_ERR_INVALID_ARG, err);
-    info->n_triangles = (uint32_t)s.tri_isect.size();
-    info->n_triangle_pairs = (uint32_t)s.pair_isect.size();
-    info->n_box_clusters = (uint32_t)(s.clusters.size() / (4 * rt::kCluF4));
-    info->pair_free_mask = s.pair_free_mask;
-    info->n_spheres = (uint32_t)s.sph_isect.size();
-    info->n_sphere_nodes = s.sph_layout_nodes;
+    rt::SceneTables t = scene_tables(s, 0, nullptr);
+    info->n_triangles = t.nT;
+    info->n_triangle_pairs = t.nP;
+    info->n_box_clusters = t.nC;
+    info->pair_free_mask = t.pair_free;
+    info->n_spheres = t.nS;
+    info->n_sphere_nodes = t.nN;
     const size_t lds = rt::kernel_lds_bytes(info->n_triangles, info->n_triangle_pairs, info->n_spheres,
                                             s.sph_layout_nodes);
     const size_t lds_single = rt::kernel_lds_bytes(info->n_triangles, 0, 0, 0);
@@ -1141,7 +1151,7 @@ int rt_scene_describe_ex(const rt_scene_desc* d, const rt_create_options* opt, r
                      (ro.mem == rt::SceneMem::kTriBvh ||
                       (ro.mem == rt::SceneMem::kAuto && (info->n_triangles > rt::kTriBvhMinTriangles ||
                                                          std::min(lds, lds_single) > rt::kMaxLdsBytes)));
-    info->n_triangle_bvh_nodes = bvh ? 2 * info->n_triangles - 1 : 0u;
+    info->n_triangle_bvh_nodes = t.nTN = bvh ? 2 * info->n_triangles - 1 : 0u;
     // the launcher takes the sphere kernel only for the pair layout (every
     // triangle paired) and no triangle BVH, with its pair copy within 6 KB
     info->sphere_kernel_lds_bytes = (rt::sphere_compact_usable(s) && info->n_triangle_pairs > 0 && !bvh &&
@@ -1150,14 +1160,12 @@ int rt_scene_describe_ex(const rt_scene_desc* d, const rt_create_options* opt, r
                                         : 0u;
     // box clusters are staged after the pairs in triangle-only scenes
     const size_t lds_clu =
-        lds + (info->n_spheres ? 0u : rt::kCluF4 * sizeof(float) * 4 * info->n_box_clusters);
+        lds + (t.nS ? 0u : 16 * rt::staged_f4<size_t>(rt::kLayPairClu, t.nT, t.nP, t.nC).clu);
     info->lds_bytes = (!bvh && lds <= rt::kMaxLdsBytes)
                           ? (uint32_t)(lds_clu <= rt::kMaxLdsBytes ? lds_clu : lds)
                           : 0u;
     // the launcher's own choice (rt::choose_kernel), for a render of >= 1 bounce
-    const rt::KernelChoice kc =
-        rt::choose_kernel(info->n_triangles, info->n_triangle_pairs, info->n_spheres, info->n_box_clusters,
-                          info->n_triangle_bvh_nodes, rt::sphere_compact_usable(s), 3, ro.mem, ro.walk);
+    const rt::KernelChoice kc = rt::choose_kernel(t, rt::sphere_compact_usable(s), 3, ro.mem, ro.walk);
     info->kernel_layout = (uint32_t)kc.layout;
     info->kernel_lds_bytes = (uint32_t)kc.lds_bytes;
     return RT_OK;

@@ -170,26 +170,16 @@ __global__ __launch_bounds__(kFreeThreads, kFreeWavesPerEu) void path_free_kerne
     __shared__ float stash[kFsSlots * kFreeThreads];
 
     SceneView sv;
-    sv.nT = P.nT;
-    sv.nP = P.nP;
-    sv.nS = SPH ? P.nS : 0u;
-    sv.nC = 0;
-    sv.htab = nullptr;
+    const SceneTables T = tables_of(P);
     if (SPH) {  // the room's pair records in LDS; the compact sphere BVH stays in L2
-        const uint32_t ng4 = kPairF4 * sv.nP;
-        RT_LDS_GUARD(16 * (size_t)ng4);
-        for (uint32_t k = threadIdx.x; k < ng4; k += kFreeThreads) lds[k] = P.pair_isect[k];
+        RT_LDS_GUARD(16 * (size_t)staged_f4(GEO, T.nT, T.nP, T.nC).rec);
+        stage_records<GEO, kFreeThreads>(lds, T);
         __syncthreads();
-        sv.tri = lds;
-        sv.pair = lds;
     }
+    bind_scene<GEO, SPH>(sv, T, lds);
     sv.sent = reinterpret_cast<const uint4*>(P.sph_lds);
     sv.sid = P.sph_lds_id;
-    sv.tnode = P.tri_nodes;
-    sv.tsorted = P.tri_sorted;
-    sv.tperm = P.tri_perm;
-    sv.nTN = P.nTN;
-    const uint32_t nLay = SPH ? P.nE : P.nTN;  // entries per octant layout
+    const uint32_t nLay = SPH ? P.nE : T.nTN;  // entries per octant layout
 
     // XCD-aware tile order (xcd_tile), one wave = one tile of 8x8 pixels, or
     // one row of 64 pixels when the rows are interleaved

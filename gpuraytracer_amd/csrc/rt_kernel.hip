@@ -619,51 +619,25 @@ void path_trace_kernel(KParams P) {
     constexpr uint32_t NT = block_threads(GEO), WR = waves_per_row(GEO), WC = waves_per_col(GEO);
     extern __shared__ float4 lds[];
     SceneView sv;
-    sv.nT = P.nT;
-    sv.nP = P.nP;
-    sv.nS = SPH ? P.nS : 0u;
-    if (GEO == kGeoPairSmem) {
-        sv.tri = nullptr;
-        sv.pair = P.pair_isect;
-    } else if (GEO != kGeoTriGlobal && GEO != kGeoTriBvh) {
-        // Stage the intersection records once per workgroup.
-        constexpr bool pairs = GEO == kGeoPairLds || GEO == kGeoPairClu || GEO == kGeoSphLds;
-        const uint32_t ng4 = pairs ? kPairF4 * sv.nP : 3u * sv.nT;
-        const float4* src = pairs ? P.pair_isect : P.tri_isect;
-        RT_LDS_GUARD(16 * (size_t)(ng4 + (GEO == kGeoPairClu ? kCluF4 * P.nC : 0u)) +
-                     (GEO == kGeoPairClu ? 4 * (size_t)kHaltonTabFloats : 0));
-        for (uint32_t k = threadIdx.x; k < ng4; k += NT) lds[k] = src[k];
-        if (GEO == kGeoSphLds) {  // the leaf-box sphere BVH (8 layouts) stays in global memory (L2)
-            sv.sbox = P.sph_box;
-            sv.nSB = P.nN;
+    const SceneTables T = tables_of(P);
+    if (geo_staged(GEO)) {
+        // Stage the intersection records once per workgroup, then the Halton tables.
+        const StagedF4<uint32_t> n = staged_f4(GEO, T.nT, T.nP, T.nC);
+        RT_LDS_GUARD(16 * (size_t)(n.rec + n.clu) + (GEO == kGeoPairClu ? 4 * (size_t)kHaltonTabFloats : 0));
+        stage_records<GEO, NT>(lds, T);
+        if (GEO == kGeoSphLds) {
             __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
             sv.xstash = sph_stash;
         }
-        if (GEO == kGeoPairClu) {  // box clusters after the pair records, then the Halton tables
-            for (uint32_t k = threadIdx.x; k < kCluF4 * P.nC; k += NT) lds[ng4 + k] = P.clusters[k];
-            const uint32_t tab0 = ng4 + kCluF4 * P.nC;
+        if (GEO == kGeoPairClu) {
+            const uint32_t tab0 = n.rec + n.clu;
             const bool tab = halton_tables_on(GEO, SMALL, P.spp, L);
             sv.htab = tab ? reinterpret_cast<const float*>(lds + tab0) : nullptr;
             if (tab) fill_halton_tables(reinterpret_cast<float*>(lds + tab0), threadIdx.x, NT);
         }
         __syncthreads();
-        sv.tri = lds;
-        sv.pair = lds;
-        sv.clu = lds + ng4;
-        sv.nC = P.nC;
-        sv.pair_free = P.pair_free;
-    } else {
-        sv.tri = P.tri_isect;
-        sv.pair = nullptr;
     }
-    sv.tnode = P.tri_nodes;
-    sv.tsorted = P.tri_sorted;
-    sv.tperm = P.tri_perm;
-    sv.nTN = P.nTN;
-    sv.node = P.sph_nodes;  // sphere BVH: scalar loads from global memory
-    sv.sph = P.sph_isect;
-    sv.nN = SPH ? P.nN : 0u;  // sphere walks: BVH nodes per layout
-    sv.sph_perm = P.sph_perm;
+    bind_scene<GEO, SPH>(sv, T, lds);
 
     // wave = 64/L pixels: 8x8 (L=1), 4x4 (L=4), 2x2 (L=16), or one row of 64/L
     // pixels for interleaved rows (launcher's wave_w); workgroup = 2x2 waves
@@ -890,27 +864,11 @@ void path_trace_sorted_kernel(
     KParams P) {
     extern __shared__ float4 lds[];
     SceneView sv;
-    sv.nT = P.nT;
-    sv.nP = P.nP;
-    sv.nS = SPH ? P.nS : 0u;
-    sv.nC = 0;
-    sv.htab = nullptr;
-    const uint32_t ng4 = GEO == kGeoTriBvh ? 0u : kPairF4 * sv.nP;
-    RT_LDS_GUARD(16 * (size_t)(kSortF4 + ng4));
+    const SceneTables T = tables_of(P);
+    RT_LDS_GUARD(16 * (size_t)(kSortF4 + staged_f4(GEO, T.nT, T.nP, T.nC).rec));
     float4* scene = lds + kSortF4;  // sort buffers first: compile-time offsets
-    for (uint32_t k = threadIdx.x; k < ng4; k += kBlockThreads) scene[k] = P.pair_isect[k];
-    sv.nN = SPH ? P.nN : 0u;
-    sv.sbox = P.sph_box;
-    sv.nSB = P.nN;
-    sv.tnode = P.tri_nodes;
-    sv.tsorted = P.tri_sorted;
-    sv.tperm = P.tri_perm;
-    sv.nTN = P.nTN;
-    sv.tri = scene;
-    sv.pair = scene;
-    sv.node = P.sph_nodes;
-    sv.sph = P.sph_isect;
-    sv.sph_perm = P.sph_perm;
+    stage_records<GEO, kBlockThreads>(scene, T);
+    bind_scene<GEO, SPH>(sv, T, scene);
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t x = blockIdx.x * kTile + (wave & 1u) * 8u + (lane & 7u);
@@ -1195,9 +1153,9 @@ size_t kernel_lds_bytes(uint32_t n_tri, uint32_t n_pairs, uint32_t n_sph, uint32
     return n_pairs ? staged_lds_bytes(kLayPairLds, n_tri, n_pairs, 0) : staged_lds_bytes(kLayTriLds, n_tri, 0, 0);
 }
 
-KernelChoice choose_kernel(uint32_t nT, uint32_t nP, uint32_t nS, uint32_t nC, uint32_t nTN, bool sph_compact,
-                           uint32_t bounces, SceneMem mem, uint32_t walk) {
-    auto lds = [&](int lay) { return staged_lds_bytes(lay, nT, nP, nC); };
+KernelChoice choose_kernel(const SceneTables& t, bool sph_compact, uint32_t bounces, SceneMem mem, uint32_t walk) {
+    const uint32_t nP = t.nP, nS = t.nS, nC = t.nC, nTN = t.nTN;
+    auto lds = [&](int lay) { return staged_lds_bytes(lay, t.nT, nP, nC); };
     const bool pairs = nP > 0 && mem != SceneMem::kLdsSingle;
     int geo = kGeoTriGlobal;
     if (mem != SceneMem::kSmem && lds(pairs ? kGeoPairLds : kGeoTriLds) <= kMaxLdsBytes)
@@ -1236,7 +1194,7 @@ KernelChoice choose_kernel(uint32_t nT, uint32_t nP, uint32_t nS, uint32_t nC, u
 namespace {
 hipError_t launch_path_trace_impl(const KParams& P, uint32_t bounces, SceneMem mem,
                                   hipStream_t stream) {
-    const KernelChoice kc = choose_kernel(P.nT, P.nP, P.nS, P.nC, P.nTN, P.sph_lds != nullptr, bounces, mem, P.walk);
+    const KernelChoice kc = choose_kernel(tables_of(P), P.sph_lds != nullptr, bounces, mem, P.walk);
     const int geo = kc.layout;
     const size_t lds_total = kc.lds_bytes;  // exactly what the layout's staging loops write
 #ifdef RT_LDS_UNDERSIZE  // negative control of the RT_LDS_CHECK build: one float4 short

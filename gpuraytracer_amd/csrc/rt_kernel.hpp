@@ -67,7 +67,30 @@ constexpr uint32_t kTriCompactLayouts = 8;
 // of the LDS brute-force layouts and the BVH walks on random triangles: ~300).
 constexpr uint32_t kTriBvhMinTriangles = 384;
 
-// Kernel arguments (passed by value -> kernarg segment / SGPRs).
+// The scene's device tables and counts, the same for every kernel of a
+// context: what the kernels build their SceneView from (rt_trace.hpp
+// tables_of, stage_records, bind_scene).
+struct SceneTables {
+    const float4* tri_isect;   // 3 float4 per triangle (TriIsect)
+    const float4* pair_isect;  // kPairF4 float4 per shared-edge triangle pair (PairIsect), or null
+    const float4* clusters;    // box clusters, kCluF4 float4 each, or null
+    const float4* sph_isect;   // 1 float4 per sphere, BVH leaf order (SphIsect)
+    const float4* sph_nodes;   // 2 float4 per sphere-BVH node (BvhNode)
+    const uint32_t* sph_perm;  // BVH leaf order -> sphere id
+    const uint4* sph_box;      // the same BVH with leaf boxes: 8 layouts x nN entries, or null
+    const uint4* tri_nodes;    // triangle BVH: 8 compact layouts x nTN nodes, or null
+    const float4* tri_sorted;  // 3 float4 per triangle, BVH leaf order
+    const uint32_t* tri_perm;  // BVH leaf order -> triangle id
+    uint32_t nT, nP, nS, nN;   // triangles, triangle pairs (0: no pair layout), spheres, sphere-BVH nodes
+    uint32_t nTN;              // triangle-BVH nodes per layout (0: no triangle BVH)
+    uint32_t nC;               // box clusters (0: none)
+    uint32_t pair_free;        // pairs in no cluster (bit mask)
+};
+// Kernel arguments (passed by value -> kernarg segment / SGPRs).  The scene
+// tables stay flat members here (tables_of, rt_trace.hpp, gathers them): with
+// them moved into one SceneTables member the spills and loop bodies of the
+// path kernels changed (profiles/r13/isa.md), unlike MisParams and
+// RayQueryParams, which embed the block.
 struct KParams {
     const float4* tri_isect;  // 3 float4 per triangle (TriIsect)
     const float4* pair_isect; // kPairF4 float4 per shared-edge triangle pair (PairIsect) or null
@@ -125,28 +148,46 @@ enum KernelLayout : int {
     kLaySortSph = 10,    // octant-sorted paths, sphere scene
     kLaySortTri = 11,    // octant-sorted paths, triangle BVH
 };
+// THE LDS order of every layout: the float4 count of the
+// records a workgroup of layout `lay` stages (pair records, or triangle records
+// for kLayTriLds; 0: the records stay in global memory) and of the box clusters
+// right after them (kLayPairClu).  What a kernel adds of its own -- Halton
+// tables, MIS shading records and stash -- follows; the sorted kernels' path
+// buffers come first.  Every LDS size below and every kernel's offsets
+// (rt_trace.hpp stage_records, bind_scene) are these two terms.
+// N: uint32_t in the kernels (LDS offsets), size_t where the host decides
+// whether a scene fits at all.
+template <typename N>
+struct StagedF4 {
+    N rec, clu;
+};
+template <typename N = uint32_t>
+__host__ __device__ __forceinline__ constexpr StagedF4<N> staged_f4(int lay, N nT, N nP, N nC) {
+    return StagedF4<N>{lay == kLayTriLds ? 3u * nT
+                       : (lay == kLayPairLds || lay == kLayPairClu || lay == kLaySphLds || lay == kLayFreeSph ||
+                          lay == kLayPairSorted || lay == kLaySortSph)
+                           ? kPairF4 * nP
+                           : N(0),  // TriGlobal, PairSmem, TriBvh, FreeTri, SortTri
+                       lay == kLayPairClu ? kCluF4 * nC : N(0)};
+}
 // LDS of the Halton low-digit tables (rt_halton.hpp kHaltonTabFloats) and of
 // the sorted kernel's path buffers (rt_kernel.hip kSortF4), static-asserted
 // against their definitions.
 constexpr uint32_t kHaltonTabLdsFloats = 4679;
 constexpr uint32_t kSortLdsF4 = 1097;
-// THE dynamic LDS of a workgroup of layout `lay`: the bytes its staging loops
-// write (pair / triangle records, then box clusters, then the Halton tables;
-// the sorted kernels' path buffers first).  The launcher requests exactly this
-// and the kernels place their staged arrays by the same terms; an
-// -DRT_LDS_CHECK build also checks it against the dispatch's LDS allocation.
+// THE dynamic LDS of a workgroup of layout `lay`: the bytes its staging writes
+// (staged_f4, then the Halton tables; the sorted kernels' path buffers first).
+// The launcher requests exactly this and the kernels place their staged arrays
+// by the same terms; an -DRT_LDS_CHECK build also checks it against the
+// dispatch's LDS allocation.
 __host__ __device__ constexpr size_t staged_lds_bytes(int lay, uint32_t nT, uint32_t nP, uint32_t nC) {
-    return lay == kLayTriLds ? (size_t)48 * nT
-           : (lay == kLayPairLds || lay == kLaySphLds || lay == kLayFreeSph) ? (size_t)16 * kPairF4 * nP
-           : lay == kLayPairClu ? (size_t)16 * (kPairF4 * nP + kCluF4 * nC) +
-                                      (size_t)4 * kHaltonTabLdsFloats
-           : (lay == kLayPairSorted || lay == kLaySortSph) ? (size_t)16 * (kSortLdsF4 + kPairF4 * nP)
-           : lay == kLaySortTri ? (size_t)16 * kSortLdsF4
-           : (size_t)0;  // TriGlobal, PairSmem, TriBvh, FreeTri: the scene stays in global memory
+    const StagedF4<size_t> n = staged_f4<size_t>(lay, nT, nP, nC);
+    return 16 * (n.rec + n.clu) + (lay == kLayPairClu ? (size_t)4 * kHaltonTabLdsFloats : (size_t)0) +
+           ((lay == kLayPairSorted || lay == kLaySortSph || lay == kLaySortTri) ? (size_t)16 * kSortLdsF4 : (size_t)0);
 }
 // The kernel layout a launch takes and its dynamic LDS (launch_path_trace and
-// rt_scene_describe_ex both ask this one function).  nC: box clusters, nTN:
-// triangle-BVH nodes per layout, sph_compact: every table of the compact
+// rt_scene_describe_ex both ask this one function).  t: the scene's counts (its
+// pointers are not read), sph_compact: every table of the compact
 // sphere kernel exists (rt_scene.hpp sphere_compact_usable; the launcher reads
 // it from P.sph_lds, which rt_api.cpp sets by that predicate).
 struct KernelChoice {
@@ -164,8 +205,7 @@ constexpr uint32_t kWalkAuto = 0, kWalkLockstep = 1, kWalkFree = 2, kWalkSorted 
 enum class SceneMem { kAuto = 0, kLdsSingle = 1, kSmem = 2, kPairSorted = 3, kPairSmem = 4, kTriBvh = 5, kPairLds = 6 };
 hipError_t launch_path_trace(const KParams& P, uint32_t bounces, SceneMem mem, hipStream_t stream,
                              LaunchInfo* info);
-KernelChoice choose_kernel(uint32_t nT, uint32_t nP, uint32_t nS, uint32_t nC, uint32_t nTN, bool sph_compact,
-                           uint32_t bounces, SceneMem mem, uint32_t walk);
+KernelChoice choose_kernel(const SceneTables& t, bool sph_compact, uint32_t bounces, SceneMem mem, uint32_t walk);
 hipError_t read_debug_stats(unsigned long long* out, int n);  // RT_STATS builds only
 // -DRT_LDS_CHECK builds: the largest staging end a kernel found past its
 // dispatch's dynamic LDS since the last call (0: none; always 0 otherwise).
@@ -173,19 +213,11 @@ hipError_t lds_check_result(uint32_t* end);
 // Arguments of the MIS integrator kernel (rt_mis.hip; Sources/gpuRaytracer/
 // shaders.metal:635-707).
 struct MisParams {
-    const float4* tri_isect;   // 3 float4 per triangle
-    const uint4* tri_nodes;    // triangle BVH or null (as KParams)
-    const float4* tri_sorted;
-    const uint32_t* tri_perm;
-    uint32_t nTN;
-    const float4* pair_isect;  // kPairF4 float4 per pair, or null
-    const float4* clusters;    // box clusters (as KParams), or null
-    uint32_t nC, pair_free;
+    SceneTables tab;           // triangle scenes only: the sphere members are null / 0
     const float4* mis_shade;   // 3 float4 per triangle (MisShade)
     const float4* u_tab;       // 3 float4 per MIS sample index i < S (Halton table)
     float4* out;               // (sum over camera rays, camera_rays) per pixel, or null
     uchar4* out8;              // writeToPixelBuffer RGBA8, or null
-    uint32_t nT, nP;
     float cam_pos[3], cam_u[3], cam_v[3], cam_w[3];
     float halfW, halfH;
     int32_t W, H;
@@ -212,26 +244,14 @@ constexpr int ray_query_layout(int lay) {
                                                         : lay;
 }
 // THE dynamic LDS of a query workgroup of layout `lay` (after ray_query_layout):
-// pair or triangle records, then the box clusters; no Halton tables.  The
-// kernel places its arrays by these terms and the launcher requests exactly this.
+// staged_f4 and nothing else (no Halton tables).  The kernel places its arrays
+// by these terms and the launcher requests exactly this.
 __host__ __device__ constexpr size_t ray_query_lds_bytes(int lay, uint32_t nT, uint32_t nP, uint32_t nC) {
-    return lay == kLayTriLds                            ? (size_t)48 * nT
-           : (lay == kLayPairLds || lay == kLaySphLds)  ? (size_t)16 * kPairF4 * nP
-           : lay == kLayPairClu                         ? (size_t)16 * (kPairF4 * nP + kCluF4 * nC)
-                                                        : (size_t)0;
+    const StagedF4<size_t> n = staged_f4<size_t>(lay, nT, nP, nC);
+    return 16 * (n.rec + n.clu);
 }
 struct RayQueryParams {
-    const float4* tri_isect;   // the scene tables, as KParams
-    const float4* pair_isect;
-    const float4* sph_isect;
-    const float4* sph_nodes;
-    const uint32_t* sph_perm;
-    const uint4* sph_box;
-    const uint4* tri_nodes;
-    const float4* tri_sorted;
-    const uint32_t* tri_perm;
-    const float4* clusters;
-    uint32_t nT, nP, nS, nN, nTN, nC, pair_free;
+    SceneTables tab;
     uint32_t sph_compact;      // every table of the sphere kernel exists (as P.sph_lds != null for a render)
     const float4* rays;        // 2 float4 per ray: (origin, tmin) (dir, tmax), device memory
     uint2* hits;               // (t bits, id) per ray, device memory

@@ -384,7 +384,7 @@ constexpr uint32_t kMisRowPixels = 64u / kMisLanes;
 #define RT_MIS_WAVES 7
 #endif
 constexpr int kMisWavesPerEu = RT_MIS_WAVES;
-// FREEP: the scene has pairs in no box cluster (P.pair_free != 0).  The
+// FREEP: the scene has pairs in no box cluster (P.tab.pair_free != 0).  The
 // reference scene has none; with FREEP false their loop is compiled out, which
 // also drops the one VGPR its loop-invariant test occupied (8 B of scratch at
 // 7 waves/SIMD, round 4).
@@ -417,47 +417,21 @@ template <int GEO, bool FREEP = true, bool SPLIT = false>
 __global__ __launch_bounds__(kBlockThreads, kMisWavesPerEu) void mis_kernel(MisParams P) {
     extern __shared__ float4 lds[];
     SceneView sv;
-    sv.nT = P.nT;
-    sv.nP = P.nP;
-    sv.nS = 0;
-    sv.nN = 0;
-    sv.node = nullptr;
-    sv.sph = nullptr;
-    sv.sph_perm = nullptr;
-    sv.tnode = P.tri_nodes;
-    sv.tsorted = P.tri_sorted;
-    sv.tperm = P.tri_perm;
-    sv.nTN = P.nTN;
-    if (GEO == kGeoTriBvh) {
-        sv.tri = nullptr;
-        sv.pair = nullptr;
-    } else if (GEO != kGeoTriGlobal) {
-        constexpr bool pairs = GEO == kGeoPairLds || GEO == kGeoPairClu;
-        const uint32_t ng4 = pairs ? kPairF4 * sv.nP : 3u * sv.nT;
-        const float4* src = pairs ? P.pair_isect : P.tri_isect;
-        for (uint32_t k = threadIdx.x; k < ng4; k += kBlockThreads) lds[k] = src[k];
-        const uint32_t nc4 = GEO == kGeoPairClu ? kCluF4 * P.nC : 0u;
-        if (GEO == kGeoPairClu)  // box clusters after the pair records
-            for (uint32_t k = threadIdx.x; k < nc4; k += kBlockThreads) lds[ng4 + k] = P.clusters[k];
+    const SceneTables& T = P.tab;
+    if (geo_staged(GEO)) {
+        stage_records<GEO, kBlockThreads>(lds, T);
         // then the shading records (3 float4 per triangle): read per lane, often
-        for (uint32_t k = threadIdx.x; k < 3u * sv.nT; k += kBlockThreads)
-            lds[ng4 + nc4 + k] = P.mis_shade[k];
-        sv.shade = lds + ng4 + nc4;
-        sv.xstash = reinterpret_cast<float*>(lds + ng4 + nc4 + 3u * sv.nT);
+        const StagedF4<uint32_t> n = staged_f4(GEO, T.nT, T.nP, T.nC);
+        for (uint32_t k = threadIdx.x; k < 3u * T.nT; k += kBlockThreads) lds[n.rec + n.clu + k] = P.mis_shade[k];
+        sv.shade = lds + n.rec + n.clu;
+        sv.xstash = reinterpret_cast<float*>(lds + n.rec + n.clu + 3u * T.nT);
         __syncthreads();
-        sv.tri = lds;
-        sv.pair = lds;
-        sv.clu = lds + ng4;
-        sv.nC = P.nC;
-        sv.pair_free = FREEP ? P.pair_free : 0u;
     } else {
-        sv.tri = P.tri_isect;
-        sv.pair = nullptr;
-    }
-    if (GEO == kGeoTriBvh || GEO == kGeoTriGlobal) {
         sv.shade = P.mis_shade;
         sv.xstash = reinterpret_cast<float*>(lds);
     }
+    bind_scene<GEO, false>(sv, T, lds);
+    if (!FREEP) sv.pair_free = 0u;
 
     // ML lanes per pixel: lane `sub` traces the camera rays i = r*ML + sub of
     // round r, and the pixel's group leader adds the ML results to the pixel's
@@ -633,7 +607,7 @@ size_t mis_part_bytes(uint32_t camera_rays, size_t pixels) {
 }
 
 size_t mis_lds_bytes(uint32_t n_tri, uint32_t n_pairs) {  // scene records + shading records
-    return (size_t)((n_pairs ? kPairF4 * n_pairs : 3u * n_tri) + 3u * n_tri) * sizeof(float4);
+    return (staged_f4<size_t>(n_pairs ? kLayPairLds : kLayTriLds, n_tri, n_pairs, 0).rec + (size_t)3 * n_tri) * sizeof(float4);
 }
 
 // Dynamic LDS above 64 KB must be allowed per kernel: a scene whose records
@@ -665,15 +639,16 @@ hipError_t launch_mis_g(const MisParams& P, size_t lds, hipStream_t stream) {
 }
 
 hipError_t launch_mis(const MisParams& P, SceneMem mem, hipStream_t stream) {
-    const bool pairs = mem != SceneMem::kLdsSingle && P.nP > 0;
-    const size_t lds = mis_lds_bytes(P.nT, pairs ? P.nP : 0u);
+    const SceneTables& T = P.tab;
+    const bool pairs = mem != SceneMem::kLdsSingle && T.nP > 0;
+    const size_t lds = mis_lds_bytes(T.nT, pairs ? T.nP : 0u);
     const bool lds_ok = mem != SceneMem::kSmem && lds <= kMaxLdsBytes;
     const size_t X = kMisStashBytes;
-    if (P.nTN > 0 && (mem == SceneMem::kTriBvh || mem == SceneMem::kAuto)) return launch_mis_g<kGeoTriBvh>(P, X, stream);
+    if (T.nTN > 0 && (mem == SceneMem::kTriBvh || mem == SceneMem::kAuto)) return launch_mis_g<kGeoTriBvh>(P, X, stream);
     if (!lds_ok) return launch_mis_g<kGeoTriGlobal>(P, X, stream);
-    const size_t lds_clu = lds + kCluF4 * P.nC * sizeof(float4);
-    if (pairs && P.nC > 0 && mem == SceneMem::kAuto && lds_clu <= kMaxLdsBytes)
-        return P.pair_free ? launch_mis_g<kGeoPairClu, true>(P, lds_clu + X, stream)
+    const size_t lds_clu = lds + staged_f4<size_t>(kLayPairClu, T.nT, T.nP, T.nC).clu * sizeof(float4);
+    if (pairs && T.nC > 0 && mem == SceneMem::kAuto && lds_clu <= kMaxLdsBytes)
+        return T.pair_free ? launch_mis_g<kGeoPairClu, true>(P, lds_clu + X, stream)
                            : launch_mis_g<kGeoPairClu, false>(P, lds_clu + X, stream);
     if (pairs) return launch_mis_g<kGeoPairLds>(P, lds + X, stream);
     return launch_mis_g<kGeoTriLds>(P, lds + X, stream);

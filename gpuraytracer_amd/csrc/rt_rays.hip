@@ -38,25 +38,25 @@ namespace {
 // records: the definition of every answer.  ANY: *id >= 0 on the first
 // accepted hit.  *best enters as the ray's tmax.
 template <bool ANY>
-__device__ __forceinline__ void exact_scan(const RayQueryParams& P, f3 o, f3 d, float tmin, float tmax,
+__device__ __forceinline__ void exact_scan(const SceneTables& T, f3 o, f3 d, float tmin, float tmax,
                                            float* best, int* id) {
-    for (uint32_t k = 0; k < P.nT; ++k) {
+    for (uint32_t k = 0; k < T.nT; ++k) {
         float t;
-        if (tri_test(P.tri_isect[3 * k], P.tri_isect[3 * k + 1], P.tri_isect[3 * k + 2], o, d, tmin, *best, &t)) {
+        if (tri_test(T.tri_isect[3 * k], T.tri_isect[3 * k + 1], T.tri_isect[3 * k + 2], o, d, tmin, *best, &t)) {
             *id = (int)k;
             if (ANY) return;
             *best = t;
         }
     }
     const float a = dot(d, d);
-    for (uint32_t k = 0; k < P.nS; ++k) {  // leaf order: ranked by (t, id)
+    for (uint32_t k = 0; k < T.nS; ++k) {  // leaf order: ranked by (t, id)
         float t;
-        if (sph_test(P.sph_isect[k], o, d, a, tmin, tmax, &t)) {
+        if (sph_test(T.sph_isect[k], o, d, a, tmin, tmax, &t)) {
             if (ANY) {
                 *id = 0;
                 return;
             }
-            const int sid = (int)(P.nT + P.sph_perm[k]);
+            const int sid = (int)(T.nT + T.sph_perm[k]);
             if (t < *best || (t == *best && sid < *id)) {
                 *best = t;
                 *id = sid;
@@ -71,47 +71,14 @@ __device__ __forceinline__ float lane_copy(float v, int src) {
 
 template <int GEO, bool SPH, bool ANY>
 __global__ __launch_bounds__(kBlockThreads) void ray_query_kernel(RayQueryParams P) {
-    constexpr bool kPairs = GEO == kGeoPairLds || GEO == kGeoPairClu || GEO == kGeoSphLds;
-    constexpr bool kStaged = kPairs || GEO == kGeoTriLds;
     extern __shared__ float4 lds[];
     SceneView sv;
-    sv.nT = P.nT;
-    sv.nP = P.nP;
-    sv.nS = SPH ? P.nS : 0u;
-    sv.tri = P.tri_isect;
-    sv.pair = P.pair_isect;  // kGeoPairSmem: scalar loads from global memory
-    sv.clu = nullptr;
-    sv.nC = 0u;
-    sv.pair_free = 0u;
-    if constexpr (kStaged) {
-        // ray_query_lds_bytes: the records, then the box clusters
-        const uint32_t ng4 = kPairs ? kPairF4 * P.nP : 3u * P.nT;
-        const float4* src = kPairs ? P.pair_isect : P.tri_isect;
-        for (uint32_t k = threadIdx.x; k < ng4; k += kBlockThreads) lds[k] = src[k];
-        if (GEO == kGeoPairClu)
-            for (uint32_t k = threadIdx.x; k < kCluF4 * P.nC; k += kBlockThreads) lds[ng4 + k] = P.clusters[k];
+    const SceneTables& T = P.tab;
+    if constexpr (geo_staged(GEO)) {  // ray_query_lds_bytes: the records, then the box clusters
+        stage_records<GEO, kBlockThreads>(lds, T);
         __syncthreads();
-        sv.tri = lds;
-        sv.pair = lds;
-        sv.clu = lds + ng4;
-        sv.nC = P.nC;
-        sv.pair_free = P.pair_free;
     }
-    sv.tnode = P.tri_nodes;
-    sv.tsorted = P.tri_sorted;
-    sv.tperm = P.tri_perm;
-    sv.nTN = P.nTN;
-    sv.node = P.sph_nodes;
-    sv.sph = P.sph_isect;
-    sv.nN = SPH ? P.nN : 0u;
-    sv.sph_perm = P.sph_perm;
-    sv.sbox = P.sph_box;
-    sv.nSB = P.nN;
-    sv.htab = nullptr;
-    sv.sent = nullptr;
-    sv.sid = nullptr;
-    sv.shade = nullptr;
-    sv.xstash = nullptr;
+    bind_scene<GEO, SPH>(sv, T, lds);
 
     const bool accel = (P.flags & kRaysExact) == 0u;
     const uint64_t base = (uint64_t)blockIdx.x * kRayChunk;
@@ -156,7 +123,7 @@ __global__ __launch_bounds__(kBlockThreads) void ray_query_kernel(RayQueryParams
                 id = qid;
             }
         }
-        if (live && !in) exact_scan<ANY>(P, o, d, tmin, tmax, &best, &id);
+        if (live && !in) exact_scan<ANY>(T, o, d, tmin, tmax, &best, &id);
         if (live) {
             uint2 h;
             if (ANY) {
@@ -203,17 +170,16 @@ template <int GEO>
 hipError_t launch_s(const RayQueryParams& P, size_t lds_bytes, hipStream_t stream) {
     if constexpr (GEO == kGeoPairClu) return launch_a<GEO, false>(P, lds_bytes, stream);
     else if constexpr (GEO == kGeoSphLds) return launch_a<GEO, true>(P, lds_bytes, stream);
-    else return P.nS > 0 ? launch_a<GEO, true>(P, lds_bytes, stream) : launch_a<GEO, false>(P, lds_bytes, stream);
+    else return P.tab.nS > 0 ? launch_a<GEO, true>(P, lds_bytes, stream) : launch_a<GEO, false>(P, lds_bytes, stream);
 }
 
 }  // namespace
 
 hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info) {
     if (P.n == 0 || P.n > 0x80000000u) return hipErrorInvalidValue;
-    const KernelChoice kc =
-        choose_kernel(P.nT, P.nP, P.nS, P.nC, P.nTN, P.sph_compact != 0u, 3, mem, kWalkLockstep);
+    const KernelChoice kc = choose_kernel(P.tab, P.sph_compact != 0u, 3, mem, kWalkLockstep);
     const int geo = ray_query_layout(kc.layout);
-    const size_t lds = ray_query_lds_bytes(geo, P.nT, P.nP, P.nC);
+    const size_t lds = ray_query_lds_bytes(geo, P.tab.nT, P.tab.nP, P.tab.nC);
     hipError_t e;
     switch (geo) {
         case kGeoTriLds: e = launch_s<kGeoTriLds>(P, lds, stream); break;

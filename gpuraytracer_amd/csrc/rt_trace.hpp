@@ -147,33 +147,86 @@ enum Geo : int {
 
 constexpr bool geo_pairs(int g) { return g == kGeoPairLds || g == kGeoPairSmem || g == kGeoSphLds; }
 
+// Every member starts null / 0: bind_scene sets the scene's members for the
+// kernel's layout, the kernel the ones only it has.
 struct SceneView {
-    const float4* tri;        // 3 float4 per triangle (single layout)
-    const float4* pair;       // kPairF4 float4 per triangle pair (pair layout)
-    const float4* sph;        // 1 float4 per sphere, BVH leaf order
-    const float4* node;       // 2 float4 per sphere-BVH node
-    const uint32_t* sph_perm; // leaf order -> sphere id (global memory)
-    const uint4* tnode;       // triangle BVH: 8 compact octant layouts of nTN nodes
-    const float4* tsorted;    // 3 float4 per triangle, BVH leaf order
-    const uint32_t* tperm;    // leaf order -> triangle id
-    uint32_t nTN;
-    uint32_t nT, nP, nS, nN;
-    const float4* clu;        // box clusters, kCluF4 float4 each (kGeoPairClu)
-    uint32_t nC;
-    uint32_t pair_free;       // pairs in no cluster: tested by every lane
+    const float4* tri = nullptr;        // 3 float4 per triangle (single layout)
+    const float4* pair = nullptr;       // kPairF4 float4 per triangle pair (pair layout)
+    const float4* sph = nullptr;        // 1 float4 per sphere, BVH leaf order
+    const float4* node = nullptr;       // 2 float4 per sphere-BVH node
+    const uint32_t* sph_perm = nullptr; // leaf order -> sphere id (global memory)
+    const uint4* tnode = nullptr;       // triangle BVH: 8 compact octant layouts of nTN nodes
+    const float4* tsorted = nullptr;    // 3 float4 per triangle, BVH leaf order
+    const uint32_t* tperm = nullptr;    // leaf order -> triangle id
+    uint32_t nTN = 0;
+    uint32_t nT = 0, nP = 0, nS = 0, nN = 0;
+    const float4* clu = nullptr;        // box clusters, kCluF4 float4 each (kGeoPairClu)
+    uint32_t nC = 0;
+    uint32_t pair_free = 0;   // pairs in no cluster: tested by every lane
     uint32_t cam_mask = 0;    // wave-uniform: pairs the wave's camera rays can hit (rt_beam.hpp), free pairs included
     bool cam_avail = false;   // cam_mask was computed (a mask of 0 is a valid answer)
     uint32_t shd_mask = 0;    // wave-uniform: pairs that can occlude the wave's bounce-0 shadow rays (rt_shaft.hpp)
     uint32_t shd_cskip = 0;   // wave-uniform: box clusters none of whose faces is in shd_mask
     bool shd_avail = false;   // shd_mask was computed (a mask of 0: no shadow ray is occluded)
-    const float* htab;       // Halton low-digit tables in LDS (kGeoPairClu)
-    const uint4* sent;        // compact sphere BVH entries (the free-running kernel): 8 octant layouts, global
-    const uint16_t* sid;      // sphere id of each compact entry (leaves), global
-    const uint4* sbox;        // the sphere BVH with leaf boxes (kGeoSphLds): 8 layouts of nSB entries
-    uint32_t nSB;
-    const float4* shade;      // MIS shading records, 3 float4 per triangle (rt_mis.hip)
-    float* xstash;            // MIS: per-lane primary hit (p, din), SoA in LDS (rt_mis.hip)
+    const float* htab = nullptr;        // Halton low-digit tables in LDS (kGeoPairClu)
+    const uint4* sent = nullptr;        // compact sphere BVH entries (the free-running kernel): 8 octant layouts, global
+    const uint16_t* sid = nullptr;      // sphere id of each compact entry (leaves), global
+    const uint4* sbox = nullptr;        // the sphere BVH with leaf boxes (kGeoSphLds): 8 layouts of nSB entries
+    uint32_t nSB = 0;
+    const float4* shade = nullptr;      // MIS shading records, 3 float4 per triangle (rt_mis.hip)
+    float* xstash = nullptr;            // MIS: per-lane primary hit (p, din), SoA in LDS (rt_mis.hip)
 };
+
+// The scene tables of the path kernels' arguments (KParams keeps them flat).
+__host__ __device__ __forceinline__ SceneTables tables_of(const KParams& P) {
+    return SceneTables{P.tri_isect, P.pair_isect, P.clusters,   P.sph_isect, P.sph_nodes, P.sph_perm,
+                       P.sph_box,   P.tri_nodes,  P.tri_sorted, P.tri_perm,  P.nT,        P.nP,
+                       P.nS,        P.nN,         P.nTN,        P.nC,        P.pair_free};
+}
+
+constexpr bool geo_staged(int g) {
+    return g == kGeoTriLds || g == kGeoPairLds || g == kGeoPairClu || g == kGeoSphLds;
+}
+
+// THE copy loop of every kernel: the workgroup's NT threads copy the layout's
+// records to lds[0 ..) and the box clusters right after them (staged_f4,
+// rt_kernel.hpp); nothing for the layouts whose records stay in global memory.
+// No barrier: the kernel stages what only it has (Halton tables, MIS shading
+// records, the sorted kernel's sums) and then synchronises once.
+template <int GEO, uint32_t NT>
+__device__ __forceinline__ void stage_records(float4* lds, const SceneTables& T) {
+    const StagedF4<uint32_t> n = staged_f4(GEO, T.nT, T.nP, T.nC);
+    const float4* src = GEO == kGeoTriLds ? T.tri_isect : T.pair_isect;
+    for (uint32_t k = threadIdx.x; k < n.rec; k += NT) lds[k] = src[k];
+    for (uint32_t k = threadIdx.x; k < n.clu; k += NT) lds[n.rec + k] = T.clusters[k];
+}
+
+// THE place that decides, per layout, where a kernel reads the scene from:
+// tri / pair / clu in the staged records at `lds` (stage_records) or in global
+// memory, and the BVH and sphere tables (always global memory, L2-resident).
+template <int GEO, bool SPH>
+__device__ __forceinline__ void bind_scene(SceneView& sv, const SceneTables& T, const float4* lds) {
+    sv.nT = T.nT;
+    sv.nP = T.nP;
+    sv.nS = SPH ? T.nS : 0u;
+    sv.tri = geo_staged(GEO) ? lds : T.tri_isect;
+    sv.pair = geo_staged(GEO) ? lds : T.pair_isect;  // kGeoPairSmem: scalar loads from global memory
+    if (GEO == kGeoPairClu) {
+        sv.clu = lds + staged_f4(GEO, T.nT, T.nP, T.nC).rec;
+        sv.nC = T.nC;
+        sv.pair_free = T.pair_free;
+    }
+    sv.tnode = T.tri_nodes;
+    sv.tsorted = T.tri_sorted;
+    sv.tperm = T.tri_perm;
+    sv.nTN = T.nTN;
+    sv.node = T.sph_nodes;  // sphere BVH: scalar loads from global memory
+    sv.sph = T.sph_isect;
+    sv.nN = SPH ? T.nN : 0u;  // sphere walks: BVH nodes per layout
+    sv.sph_perm = T.sph_perm;
+    sv.sbox = T.sph_box;  // the leaf-box sphere BVH (kGeoSphLds)
+    sv.nSB = T.nN;
+}
 
 // Per-ray data of the slab test.  1/d uses the 1-ulp hardware reciprocal: the
 // node boxes carry the culling margin, so only speed depends on its rounding.

@@ -2,7 +2,7 @@
 # Device-code identity of the working tree against a git revision (no GPU
 # needed): the gate of a refactor that must not change an instruction.
 #   tools/isa_diff.sh <git-rev>
-# Each of the four .hip files is compiled to gfx950 assembly with the
+# Each of the five .hip files is compiled to gfx950 assembly with the
 # Makefile's HIPFLAGS, once from the working tree and once from a temporary
 # git worktree of <rev> (removed afterwards), and the two .s files are
 # compared byte for byte.  Both sides get the same -cuid=: by default hipcc
@@ -10,7 +10,7 @@
 # path, the only path-dependent text in the assembly.  One line per
 # file: identical (with the sha256 of the .s), or the symbol that holds the
 # first difference.  Exit status 1 on any difference.  rt_kernel.hip takes
-# minutes per compile; the eight compiles run ISA_JOBS (default 4) at a time.
+# minutes per compile; the ten compiles run ISA_JOBS (default 4) at a time.
 set -eu
 [ $# -eq 1 ] || { echo "usage: $0 <git-rev>" >&2; exit 2; }
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -18,7 +18,7 @@ T=$(mktemp -d)
 trap 'git -C "$R" worktree remove --force "$T/rev" >/dev/null 2>&1 || true; rm -rf "$T"' EXIT
 git -C "$R" worktree add --detach "$T/rev" "$1" >/dev/null
 CC=$(make -s -C "$R" --eval 'isa-cc: ; @echo $(HIPCC) $(HIPFLAGS)' isa-cc)
-FILES="rt_kernel rt_mis rt_lbvh rt_gsah"
+FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah"
 mkdir -p "$T/new" "$T/old"
 export T CC
 for f in $FILES; do
