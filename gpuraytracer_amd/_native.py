@@ -221,6 +221,8 @@ SIGNATURES = {
                                    [_P, ctypes.POINTER(ctypes.c_int32)]),
     "rt_debug_cluster_kinds": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(ctypes.c_uint32),
                                               ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "rt_debug_light_mask": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(ctypes.c_uint64), _P,
+                                           ctypes.c_uint32]),
 }
 
 

@@ -52,6 +52,7 @@ struct rt_ctx {
     uint32_t tri_bvh_nodes = 0;      // per layout
     rt::SceneTables tab{};           // what every kernel traces through: set once by rt_create_ex (scene_tables)
     bool sph_compact = false;        // rt_scene.hpp sphere_compact_usable: the sphere kernel's tables exist
+    uint64_t light_mask = 0;         // rt_scene.hpp light_mask: the box-cluster kernel's light flags
     uint32_t tri_bvh_build_used = 0; // rt_tri_bvh_build of the built tree (0: none)
     float tri_bvh_build_ms = 0.0f;   // wall time of the triangle-BVH build
     size_t tri_bvh_temp_bytes = 0;   // peak temporaries of the GPU SAH build
@@ -296,6 +297,7 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     memset(&K, 0, sizeof(K));
     set_tables(&K, c->tab);
     K.tri_shade = c->d_tri_shade;
+    K.light_mask = c->light_mask;
     // both compact tables or neither: the launcher takes the sphere kernel when
     // sph_lds is set, and that kernel's walks read sph_box (scene_tables)
     K.sph_lds = c->sph_compact ? c->d_sph_lds : nullptr;
@@ -894,6 +896,7 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
     }
     c->sph_compact = rt::sphere_compact_usable(c->scene);
     c->tab = scene_tables(c->scene, c->tri_bvh_nodes, c);
+    c->light_mask = rt::light_mask(c->scene);
     *out_ctx = c;
     return RT_OK;
 }
@@ -1244,6 +1247,20 @@ int rt_debug_cluster_kinds(const rt_scene_desc* d, uint32_t* flags, uint32_t cap
     const size_t rec = 4 * rt::kCluF4, nC = s.clusters.size() / rec;
     *n_clusters = (uint32_t)nC;
     for (size_t c = 0; c < nC && c < capacity; ++c) memcpy(&flags[c], &s.clusters[c * rec + 15], 4);
+    return RT_OK;
+}
+
+int rt_debug_light_mask(const rt_scene_desc* d, uint64_t* mask, float* records, uint32_t capacity_triangles) {
+    if (!d || !mask || (!records && capacity_triangles) || !d->camera || !d->square_lights)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    rt::CompiledScene s;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0],
+                           d->spheres, d->n_spheres, &s, &err))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    *mask = rt::light_mask(s);
+    for (size_t k = 0; k < s.tri_shade.size() && k < capacity_triangles; ++k)
+        memcpy(records + 16 * k, s.tri_shade[k].s, sizeof(s.tri_shade[k].s));
     return RT_OK;
 }
 

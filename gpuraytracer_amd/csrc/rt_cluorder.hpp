@@ -25,15 +25,17 @@
 // (rt_kernel.hpp has the switch's description).
 // RT_CLU_LEAN_ITEMS is the set of items built: 1 turned boxes, 2 containers
 // left from inside, 4 the light's own cluster in shadow queries.  The kernel
-// ships item 2 alone: items 1 and 4, each on its own, spill 12 and 8 VGPRs of
-// the box-cluster kernel (72 VGPRs, 7 waves/SIMD) to scratch; they stay for
-// measurements and are checked on the host (tests/test_lean_filter.py builds
-// its checker with all three).
+// ships items 2 and 4: item 4 spilled 8 VGPRs of the box-cluster kernel (72
+// VGPRs, 7 waves/SIMD) while shade() loaded the light flag of the shading
+// record first; with the flag taken from the launch's light mask (DESIGN.md
+// §3.21) it spills none.  Item 1 spills 12; it stays for measurements and is
+// checked on the host (tests/test_lean_filter.py builds its checker with all
+// three).
 #ifndef RT_CLU_LEAN
 #define RT_CLU_LEAN 1
 #endif
 #ifndef RT_CLU_LEAN_ITEMS
-#define RT_CLU_LEAN_ITEMS 2
+#define RT_CLU_LEAN_ITEMS 6
 #endif
 
 namespace rt {

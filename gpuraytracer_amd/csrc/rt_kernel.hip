@@ -4,7 +4,9 @@
 //   * the scene's intersection records (shared-edge triangle pairs, box
 //     clusters) and the Halton low-digit tables are staged into LDS once per
 //     workgroup; the sphere and triangle BVHs are read from global memory
-//     (L2-resident); shading records are fetched from global only on a hit;
+//     (L2-resident); shading records are fetched from global only on a hit (the
+//     box-cluster kernel knows a light from the launch's light mask,
+//     DESIGN.md §3.21);
 //   * L = 4 or 16 lanes per pixel: a wave traces 64/L pixels (a 4x4 or 2x2
 //     tile, or one row of interleaved rows), lane `sub` traces samples
 //     n = r*L + sub, and the colours are summed at the pixel's leader in
@@ -105,7 +107,24 @@ template <int b, int B, int GEO, bool SPH, bool SMALL, bool FUSE = false, bool S
 __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, PathState& s, int id,
                                       float t, int* nid = nullptr, float* nt = nullptr) {
     f3 N, right, fwd, diffuse;
-    if (!SPH || (uint32_t)id < sv.nT) {
+    // The box-cluster kernel (at most 31 pairs, ids < 62): the
+    // light flag is bit id of the launch's light mask (one 64-bit shift), so
+    // the gather of the record does not wait for a first load of its flag
+    // word: a light lane reads its emissive row and ends, the others the
+    // three other rows and the last colour word in one stage.
+    if constexpr (GEO == kGeoPairClu && !SPH) {
+        if ((P.light_mask >> (uint32_t)id) & 1ull) {        // :57-60 light: overwrite, stop
+            const float4 s3 = P.tri_shade[4 * id + 3];
+            s.acc = f3{s3.x, s3.y, s3.z};
+            return false;
+        }
+        const float4* sh = P.tri_shade + 4 * id;
+        const float4 s0 = sh[0], s1 = sh[1], s2 = sh[2];
+        N = f3{s0.x, s0.y, s0.z};
+        right = f3{s1.x, s1.y, s1.z};
+        fwd = f3{s2.x, s2.y, s2.z};
+        diffuse = f3{s1.w, s2.w, sh[3].w};
+    } else if (!SPH || (uint32_t)id < sv.nT) {
         const float4* sh = P.tri_shade + 4 * id;
         const float4 s0 = sh[0];
         const float4 s3 = sh[3];

@@ -129,6 +129,8 @@ struct KParams {
     const float4* clusters;   // box clusters, kCluF4 float4 each, or null
     uint32_t nC;              // clusters (0: none)
     uint32_t pair_free;       // pairs in no cluster (bit mask)
+    uint64_t light_mask;      // box-cluster kernel: bit id set when triangle id is a light, i.e. its
+                              // TriShade s0.w != 0 (ids < 64; rt_scene.hpp light_mask)
 };
 
 size_t kernel_lds_bytes(uint32_t n_tri, uint32_t n_pairs, uint32_t n_sph, uint32_t n_nodes);

@@ -1123,6 +1123,14 @@ static void build_clusters(CompiledScene* out, const rt_float3* verts, uint32_t 
     out->pair_free_mask = free_mask;
 }
 
+uint64_t light_mask(const CompiledScene& s) {
+    uint64_t m = 0;
+    if (s.tri_shade.size() > 64) return 0;
+    for (size_t id = 0; id < s.tri_shade.size(); ++id)
+        if (s.tri_shade[id].s[3] != 0.0f) m |= 1ull << id;
+    return m;
+}
+
 static bool finite3(const rt_float3& v) {
     return isfinite(v.x) && isfinite(v.y) && isfinite(v.z);
 }

@@ -140,6 +140,11 @@ inline bool sphere_compact_usable(const CompiledScene& s) {
     return !s.sph_lds.empty() && !s.sph_box.empty();
 }
 
+// Bit id set when triangle id is a light (its TriShade s0.w != 0): what the
+// box-cluster kernel tests instead of loading the flag.
+// Scenes of at most 64 triangles (box clusters: at most 31 pairs), else 0.
+uint64_t light_mask(const CompiledScene& s);
+
 constexpr uint32_t kTriLeafMax = 1;  // triangles per leaf of the host SAH build (default)
 // Host binned-SAH triangle BVH in the compact 8-octant layout (rt_scene.cpp):
 // nodes = 8 layouts x (nodes per layout) entries of 4 words, sorted = records in leaf order,

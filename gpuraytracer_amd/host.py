@@ -288,6 +288,16 @@ class Scene:
         _check(lib.rt_debug_cluster_kinds(ctypes.byref(self.desc()), flags, 32, ctypes.byref(n)))
         return [int(flags[c]) for c in range(n.value)]
 
+    def light_mask(self):
+        """``(mask, records)``: the light mask the box-cluster kernel tests
+        (rt_debug_light_mask; bit id: triangle id is a light)
+        and the (n_triangles, 16) float32 shading records it is made from."""
+        n = self.n_triangles
+        mask = ctypes.c_uint64()
+        rec = (ctypes.c_float * (16 * n))()
+        _check(lib.rt_debug_light_mask(ctypes.byref(self.desc()), ctypes.byref(mask), rec, n))
+        return int(mask.value), np.frombuffer(rec, np.float32).reshape(-1, 16).copy()
+
     def ray_domain(self) -> dict:
         """The exactness domain of ``Renderer.trace_rays`` for this scene
         (rt_debug_ray_domain): ``origin_max``,

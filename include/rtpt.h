@@ -485,6 +485,14 @@ int rt_debug_shadow_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x
  * when capacity is 0); *n_clusters: how many the scene has (at most 31). */
 int rt_debug_cluster_kinds(const rt_scene_desc* scene, uint32_t* flags, uint32_t capacity, uint32_t* n_clusters);
 
+/* Debug (host-only): the light mask the box-cluster kernel tests instead of
+ * loading a hit triangle's light flag: bit id of *mask is set
+ * when triangle id is a light (scenes of at most 64 triangles, else 0).
+ * records: room for capacity_triangles of the 64-B shading records the mask is
+ * made from, 16 floats per triangle id: (N, light) (right, diffuse.r)
+ * (fwd, diffuse.g) (emissive, diffuse.b) (may be null when that is 0). */
+int rt_debug_light_mask(const rt_scene_desc* scene, uint64_t* mask, float* records, uint32_t capacity_triangles);
+
 /* The reference's image epilogue (RTrace/image.swift:35-65): fp16 round trip,
  * ×2 exposure, Reinhard, gamma 1/2.2, clamp, truncating UInt8, alpha 255.
  * in: n_pixels rgba32F (host), out: n_pixels*4 bytes. */
