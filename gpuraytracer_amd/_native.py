@@ -109,6 +109,7 @@ WALKS = {"auto": 0, "lockstep": 1, "free": 2, "sorted": 3}
 RT_OK = 0
 RT_OUT_DEVICE, RT_OUT_FP16, RT_OUT_NONE, RT_KEEP_SUM, RT_OUT_RGBA8 = 0x1, 0x2, 0x4, 0x8, 0x10
 RT_RAYS_ANY, RT_RAYS_EXACT = 0x100, 0x200
+RT_AOV_CENTER = 0x400  # rt_render_aov: one ray through every pixel centre
 RT_RAYS_CHUNK = 2048  # consecutive rays one workgroup of the query kernel traces
 RT_MAX_BOUNCES = 4
 RT_COMM_ID_BYTES = 128
@@ -153,6 +154,19 @@ class RayDomainInfo(ctypes.Structure):  # rt_ray_domain_info
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 8 and Ray.dir.offset == 16
 
 
+class AovParams(ctypes.Structure):  # rt_aov_params
+    _fields_ = [(n, ctypes.c_uint32) for n in
+                ("spp", "sample_base", "row_start", "row_step", "row_count", "flags")]
+
+
+class AovBuffers(ctypes.Structure):  # rt_aov_buffers
+    _fields_ = [("albedo", ctypes.c_void_p), ("normal_depth", ctypes.c_void_p),
+                ("first_hit", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(AovParams) == 24 and ctypes.sizeof(AovBuffers) == 24
+
+
 class MisParamsC(ctypes.Structure):  # rt_mis_params
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("camera_rays", "mis_samples", "row_start", "row_step", "row_count", "flags")]
@@ -171,6 +185,8 @@ SIGNATURES = {
     "rt_render_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P]),
     "rt_trace_rays": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P]),
     "rt_trace_rays_async": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
+    "rt_render_aov": (ctypes.c_int, [_P, ctypes.POINTER(AovParams), ctypes.POINTER(AovBuffers)]),
+    "rt_render_aov_async": (ctypes.c_int, [_P, ctypes.POINTER(AovParams), ctypes.POINTER(AovBuffers), _P]),
     "rt_debug_ray_domain": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(RayDomainInfo)]),
     "rt_last_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_destroy": (ctypes.c_int, [_P]),

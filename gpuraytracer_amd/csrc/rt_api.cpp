@@ -66,6 +66,8 @@ struct rt_ctx {
     size_t rays_cap = 0;
     void* d_hits = nullptr;
     size_t hits_cap = 0;
+    void* d_aov[3] = {nullptr, nullptr, nullptr};  // staging for host feature buffers (rt_render_aov)
+    size_t aov_cap[3] = {0, 0, 0};
     void* d_mis_part = nullptr;    // per-ray MIS results of a split launch (rt_mis.hip)
     size_t mis_part_cap = 0;
     uint32_t* d_seeds = nullptr;
@@ -210,6 +212,7 @@ void release(rt_ctx* c) {
     (void)hipFree(c->d_mis_part);
     (void)hipFree(c->d_rays);
     (void)hipFree(c->d_hits);
+    for (void* b : c->d_aov) (void)hipFree(b);
     (void)hipFree(c->d_seeds);
     (void)hipFree(c->d_sum);
     (void)hipFree(c->d_out);
@@ -680,6 +683,89 @@ int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, r
     return RT_OK;
 }
 
+// rt_render_aov / rt_render_aov_async: one launch of the feature-buffer kernel
+// (rt_aov.hip) over the context's tables and shading records.  Host buffers go
+// through the context's staging buffers on its own stream.
+int render_aov_impl(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b, bool dev, hipStream_t stream,
+                    bool sync) {
+    static_assert(sizeof(rt_aov_params) == 24 && sizeof(rt_aov_buffers) == 24, "rt_aov_params / rt_aov_buffers layout");
+    if (!p) return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: params is null");
+    if (!b) return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: buffers is null");
+    if (!b->albedo && !b->normal_depth && !b->first_hit)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: all three buffers are null");
+    if (p->flags & ~(uint32_t)(RT_OUT_DEVICE | RT_AOV_CENTER))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: unknown flag bits");
+    if (p->spp == 0 || p->spp > (1u << 24))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: spp must be in [1, 2^24] (the coverage sum stays exact)");
+    const bool center = (p->flags & RT_AOV_CENTER) != 0;
+    if (center && p->spp != 1) return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: RT_AOV_CENTER needs spp == 1");
+    rt_render_params rows{};
+    rows.row_start = p->row_start;
+    rows.row_step = p->row_step;
+    rows.row_count = p->row_count;
+    uint32_t start, step, count;
+    if (!resolve_rows(c, &rows, &start, &step, &count))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: row partition outside the frame");
+    if (!center && !c->seeds_ready)
+        return fail(c, RT_ERR_STATE, "rt_render_aov: seeds not set (rt_set_seeds/rt_fill_seeds)");
+
+    const size_t pixels = (size_t)count * (size_t)c->scene.cam.W;
+    void* host[3] = {b->albedo, b->normal_depth, b->first_hit};
+    const size_t bytes[3] = {pixels * sizeof(float4), pixels * sizeof(float4), pixels * sizeof(rt_ray_hit)};
+    void* kbuf[3] = {host[0], host[1], host[2]};
+    if (!dev) {
+        for (int k = 0; k < 3; ++k) {
+            if (!host[k]) continue;
+            const int st = ensure_staging(c, &c->d_aov[k], &c->aov_cap[k], bytes[k], "hipMalloc(aov staging)");
+            if (st != RT_OK) return st;
+            kbuf[k] = c->d_aov[k];
+        }
+    }
+    rt::AovParams K;
+    memset(&K, 0, sizeof(K));
+    K.tab = c->tab;
+    K.sph_compact = c->sph_compact ? 1u : 0u;
+    K.tri_shade = c->d_tri_shade;
+    K.sph_shade = c->d_sph_shade;
+    K.seeds = center ? nullptr : c->d_seeds;
+    K.albedo = static_cast<float4*>(kbuf[0]);
+    K.normal_depth = static_cast<float4*>(kbuf[1]);
+    K.first_hit = static_cast<uint2*>(kbuf[2]);
+    const rt::CamConst& cam = c->scene.cam;
+    memcpy(K.cam_pos, cam.pos, sizeof(K.cam_pos));
+    memcpy(K.cam_u, cam.u, sizeof(K.cam_u));
+    memcpy(K.cam_v, cam.v, sizeof(K.cam_v));
+    memcpy(K.cam_w, cam.w, sizeof(K.cam_w));
+    K.halfW = cam.halfW;
+    K.halfH = cam.halfH;
+    K.W = cam.W;
+    K.H = cam.H;
+    K.spp = p->spp;
+    K.sample_base = center ? 0u : p->sample_base;
+    K.row_start = start;
+    K.row_step = step;
+    K.row_count = count;
+    K.flags = center ? rt::kAovCenter : 0u;
+    if (!center) {
+        const uint64_t imax = (uint64_t)c->seed_max + p->sample_base + (p->spp - 1u);
+        K.max_index = imax > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)imax;
+    }
+    (void)hipEventRecord(c->ev0, stream);
+    hipError_t e = rt::launch_aov(K, c->scene_mem, stream, &c->launch);
+    if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "aov launch", e);
+    c->launched = true;
+    (void)hipEventRecord(c->ev1, stream);
+    c->timed = true;
+    if (!dev) {
+        for (int k = 0; k < 3; ++k)
+            if (host[k] && (e = hipMemcpyAsync(host[k], kbuf[k], bytes[k], hipMemcpyDeviceToHost, stream)) != hipSuccess)
+                return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(aov)", e);
+    }
+    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "aov execution", e);
+    return RT_OK;
+}
+
 // rt_create_options (include/rtpt.h) -> the context's choices and the host
 // builds' options.  False (with *why) for a value outside its range.
 struct Resolved {
@@ -954,6 +1040,18 @@ int rt_trace_rays_async(rt_ctx* c, const rt_ray* rays_dev, uint64_t n, uint32_t 
     if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
     DeviceGuard g(c->device);
     return trace_rays_impl(c, rays_dev, n, flags, hits_dev, true, (hipStream_t)hip_stream, false);
+}
+
+int rt_render_aov(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return render_aov_impl(c, p, b, p && (p->flags & RT_OUT_DEVICE), c->stream, true);
+}
+
+int rt_render_aov_async(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b_dev, void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return render_aov_impl(c, p, b_dev, true, (hipStream_t)hip_stream, false);
 }
 
 int rt_debug_ray_domain(const rt_scene_desc* d, rt_ray_domain_info* info) {

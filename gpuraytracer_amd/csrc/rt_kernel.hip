@@ -32,6 +32,7 @@
 #include "rt_halton.hpp"
 #include "rt_beam.hpp"
 #include "rt_shaft.hpp"
+#include "rt_pixel.hpp"
 #include "rt_trace.hpp"
 
 namespace rt {
@@ -438,39 +439,6 @@ __device__ __forceinline__ void finish_pixel(const KParams& P, size_t o, f3 lum)
     }
 }
 
-// generateCameraRay (sampling.metal:125-157): the direction through pixel
-// (fx, fy) jittered by (jx, jy).  IEEE: the triangle-BVH kernel's
-// normalize_ieee (rt_math.h).
-template <bool IEEE = false>
-__device__ __forceinline__ f3 camera_dir(const KParams& P, f3 cu, f3 cv, f3 cw, float fW, float fH, float fx,
-                                         float fy, float jx, float jy) {
-    const float sx = ((fx + jx) / fW) * 2.0f - 1.0f;
-    const float ty = -(((fy + jy) / fH) * 2.0f - 1.0f);
-    const float sh = sx * P.halfW, th = ty * P.halfH;
-    return IEEE ? normalize_ieee((cu * sh + cv * th) - cw) : normalize((cu * sh + cv * th) - cw);
-}
-
-// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs in
-// dispatch order (p = blockIdx.y * gridDim.x + blockIdx.x; MI355X_MICROARCH.md
-// "Workgroup dispatch"), so the tiles are dealt in runs of kXcdRun: the run
-// of neighbouring tiles that share the 128-B lines of the seed rows goes
-// through ONE XCD's L2 (seed reads 4x -> 1x the seed bytes), while the runs
-// still interleave over the XCDs, which keeps the cheap and the expensive
-// image regions evenly spread (contiguous bands per XCD ran 7 % slower).
-// Speed only: every tile is rendered exactly once.
-__device__ __forceinline__ void xcd_tile(uint32_t& bx, uint32_t& by) {
-    constexpr uint32_t kXcdRun = 4;  // runs of 0 (plain order) / 16: 158.9 / 157.6 vs 158.4 ms on config 4
-    const uint32_t n = gridDim.x * gridDim.y, full = n / (8u * kXcdRun + (kXcdRun == 0)) * (8u * kXcdRun);
-    const uint32_t p = blockIdx.y * gridDim.x + blockIdx.x;
-    uint32_t t = p;
-    if (kXcdRun > 0 && p < full) {
-        const uint32_t xcd = p % 8u, k = p / 8u;
-        t = ((k / kXcdRun) * 8u + xcd) * kXcdRun + k % kXcdRun;
-    }
-    bx = t % gridDim.x;
-    by = t / gridDim.x;
-}
-
 // ---- sorted-path variant ----------------------------------------------------
 // Between bounces the 256 paths of a workgroup are counting-sorted through LDS
 // by the octant of their next direction, dead paths last (9 buckets).  Waves
@@ -598,14 +566,6 @@ struct SortedChain<B, B, GEO, SPH, SMALL> {
 
 constexpr int kMinWavesPerEu = 8;     // 8 waves/SIMD (<= 64 VGPRs): +4.5% measured over 7
 constexpr int kMinWavesPerEuSph = 8;  // sphere kernel: 7 / 6 waves 162.2 / 176.3 ms vs 154.3
-constexpr uint32_t kHaltonTabMinRounds = 8;  // samples per lane below which no tables
-// Whether a launch fills the LDS low-digit Halton tables: box-cluster kernel,
-// fixed-digit indices, and every lane tracing enough samples to amortise the
-// fill (~700 VALU per thread): config 1 (1 spp) runs without them.  The kernel
-// and the launcher's rt_last_launch report share this one definition.
-__host__ __device__ constexpr bool halton_tables_on(int geo, bool small, uint32_t spp, uint32_t L) {
-    return geo == kGeoPairClu && small && (spp + L - 1) / L >= kHaltonTabMinRounds;
-}
 // box-cluster kernel: 7 waves/SIMD runs as fast as 8 and spills 6 VGPRs
 // instead of 30 (HBM traffic 146 MB instead of 19 GB per 1080p launch)
 #ifndef RT_CLU_WAVES
@@ -663,6 +623,9 @@ void path_trace_kernel(KParams P) {
     const uint32_t kWX = (L == 1) ? 8u : P.wave_w, kWY = (64u / L) / kWX;
     uint32_t bx, by;
     xcd_tile(bx, by);
+    // tile_pixel (rt_pixel.hpp) for L lanes per pixel, spelled out: through the
+    // helper the compiler orders the operands of one add differently
+    // (tools/isa_diff.sh)
     auto pixel_of = [&](uint32_t t, uint32_t& x, uint32_t& j) {
         const uint32_t lane = t & 63u, wave = t >> 6, pix = lane / L;
         x = bx * (WR * kWX) + (wave % WR) * kWX + (pix % kWX);

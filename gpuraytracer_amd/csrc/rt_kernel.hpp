@@ -187,6 +187,15 @@ __host__ __device__ constexpr size_t staged_lds_bytes(int lay, uint32_t nT, uint
     return 16 * (n.rec + n.clu) + (lay == kLayPairClu ? (size_t)4 * kHaltonTabLdsFloats : (size_t)0) +
            ((lay == kLayPairSorted || lay == kLaySortSph || lay == kLaySortTri) ? (size_t)16 * kSortLdsF4 : (size_t)0);
 }
+constexpr uint32_t kHaltonTabMinRounds = 8;  // samples per lane below which no tables
+// Whether a launch fills the LDS low-digit Halton tables: box-cluster kernel,
+// fixed-digit indices, and every lane tracing enough samples to amortise the
+// fill (~700 VALU per thread): config 1 (1 spp) runs without them.  The kernels
+// (render and AOV) and the launchers' rt_last_launch reports share this one
+// definition.
+__host__ __device__ constexpr bool halton_tables_on(int geo, bool small, uint32_t spp, uint32_t L) {
+    return geo == kLayPairClu && small && (spp + L - 1) / L >= kHaltonTabMinRounds;
+}
 // The kernel layout a launch takes and its dynamic LDS (launch_path_trace and
 // rt_scene_describe_ex both ask this one function).  t: the scene's counts (its
 // pointers are not read), sph_compact: every table of the compact
@@ -262,6 +271,38 @@ struct RayQueryParams {
     RayDomain dom;             // rt_raydomain.h
 };
 hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info);
+
+// ---- first-hit feature buffers (rt_aov.hip; include/rtpt.h rt_render_aov) ---
+constexpr uint32_t kAovCenter = 0x400u;  // RT_AOV_CENTER
+// The AOV kernel draws Halton dimensions 0 and 1 only; dimension 0 is a bit
+// reversal, so the one low-digit table it stages is dimension 1's (3^6 floats,
+// the first of rt_halton.hpp's tables; static-asserted in rt_aov.hip).
+constexpr uint32_t kAovTabLdsFloats = 729;
+// THE dynamic LDS of an AOV workgroup of layout `lay` (after ray_query_layout):
+// staged_f4, then the Halton table when the launch fills it (halton_tables_on
+// at one lane per pixel).  The kernel places its arrays by these terms and the
+// launcher requests exactly this.
+__host__ __device__ constexpr size_t aov_lds_bytes(int lay, uint32_t nT, uint32_t nP, uint32_t nC, bool tables) {
+    return ray_query_lds_bytes(lay, nT, nP, nC) + (tables ? (size_t)4 * kAovTabLdsFloats : (size_t)0);
+}
+struct AovParams {
+    SceneTables tab;
+    uint32_t sph_compact;      // every table of the sphere kernel exists (as for a query)
+    const float4* tri_shade;   // 4 float4 per triangle (TriShade)
+    const float4* sph_shade;   // 3 float4 per sphere, by id (SphShade)
+    const uint32_t* seeds;     // W*H, full frame; not read with kAovCenter
+    float4* albedo;            // (sum diffuse, sum hits) / spp per pixel, or null
+    float4* normal_depth;      // (sum N, sum t) / spp per pixel, or null
+    uint2* first_hit;          // (t bits, id) of sample sample_base per pixel, or null
+    float cam_pos[3], cam_u[3], cam_v[3], cam_w[3];
+    float halfW, halfH;
+    int32_t W, H;
+    uint32_t spp, sample_base;
+    uint32_t row_start, row_step, row_count;
+    uint32_t flags;            // kAovCenter
+    uint32_t max_index;        // max Halton index seed+n of this launch (0xFFFFFFFF: unknown/wraps)
+};
+hipError_t launch_aov(const AovParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info);
 
 hipError_t launch_mis(const MisParams& P, SceneMem mem, hipStream_t stream);
 size_t mis_lds_bytes(uint32_t n_tri, uint32_t n_pairs);

@@ -18,9 +18,9 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from ._native import (LAYOUTS, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
+from ._native import (LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, TRI_BUILDS, WALKS,
-                      BuildStats, CameraGPU, CreateOptions, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
+                      AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
                       RenderParamsC,
                       RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, float3,
                       lib)
@@ -481,6 +481,62 @@ class Renderer:
         if cur is not None:
             cur.synchronize()
         return hits[:, 0].view(torch.float32), hits[:, 1]
+
+    def render_aov(self, spp: int = 1, sample_base: int = 0, row_start: int = 0, row_step: int = 1,
+                   row_count: int = 0, center: bool = False, albedo: bool = True,
+                   normal_depth: bool = True, first_hit: bool = True, out=None, stream=None) -> dict:
+        """First-hit feature buffers (rt_render_aov) of the
+        camera rays of samples ``[sample_base, sample_base + spp)``: a dict with
+        ``albedo`` (rows, W, 4) float32 = (mean diffuse.rgb, coverage),
+        ``normal_depth`` (rows, W, 4) float32 = (mean N.xyz, mean t; misses
+        count as zero) and ``first_hit`` (rows, W) structured ``(t, id)`` of
+        sample ``sample_base`` (a miss: t = 1000, id = -1), for the buffers
+        asked for.  ``center``: one ray through every pixel centre (spp 1, no
+        seeds needed) -- the picking / id-buffer form.
+
+        ``out``: a dict of contiguous torch tensors on the context's device,
+        (rows, W, 4) float32 under ``albedo`` / ``normal_depth`` and (rows, W, 2)
+        int32 (t bits, id) under ``first_hit``; only its keys are rendered, on
+        ``stream`` without a host sync (default: torch's current stream, then
+        waited for).  Returns ``out``."""
+        p = AovParams()
+        p.spp, p.sample_base = spp, sample_base
+        p.row_start, p.row_step, p.row_count = row_start, row_step, row_count
+        p.flags = RT_AOV_CENTER if center else 0
+        rows = RenderParams(row_start=row_start, row_step=row_step, row_count=row_count).rows(self.scene.height)
+        W = self.scene.width
+        b = AovBuffers()
+        if out is None:
+            res = {}
+            if albedo:
+                res["albedo"] = np.empty((rows, W, 4), np.float32)
+            if normal_depth:
+                res["normal_depth"] = np.empty((rows, W, 4), np.float32)
+            if first_hit:
+                res["first_hit"] = np.empty((rows, W), np.dtype([("t", np.float32), ("id", np.int32)]))
+            for k, a in res.items():
+                setattr(b, k, a.ctypes.data)
+            _check(lib.rt_render_aov(self._ctx, ctypes.byref(p), ctypes.byref(b)), self._ctx)
+            return res
+        import torch  # plumbing only: device memory and the caller's stream
+        shapes = {"albedo": ((rows, W, 4), torch.float32), "normal_depth": ((rows, W, 4), torch.float32),
+                  "first_hit": ((rows, W, 2), torch.int32)}
+        for k, t in out.items():
+            if k not in shapes:
+                raise ValueError(f"unknown buffer {k!r}")
+            shape, dt = shapes[k]
+            if (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or not t.is_cuda
+                    or t.device.index != self.device):
+                raise ValueError(f"out[{k!r}] must be a contiguous {shape} {dt} tensor on the context's device")
+            setattr(b, k, t.data_ptr())
+        p.flags |= RT_OUT_DEVICE
+        cur = torch.cuda.current_stream(self.device) if stream is None else None
+        handle = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        _check(lib.rt_render_aov_async(self._ctx, ctypes.byref(p), ctypes.byref(b), ctypes.c_void_p(handle)),
+               self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        return out
 
     def render_progressive(self, params: RenderParams, batch_spp: int, out, stream=None,
                            gather: bool = False):

@@ -249,8 +249,8 @@ int rt_place_tiles(rt_ctx* ctx, const void* gathered_device, int32_t world, uint
 int rt_place_tiles_host(const void* gathered, int32_t width, int32_t height, int32_t world,
                         uint32_t flags, void* frame);
 
-/* Which kernel instantiation the most recent rt_render/rt_render_async or
- * rt_trace_rays/rt_trace_rays_async launched, with its launch shape: lets a caller (bench, tests) state which
+/* Which kernel instantiation the most recent rt_render/rt_render_async,
+ * rt_trace_rays/rt_trace_rays_async or rt_render_aov/rt_render_aov_async launched, with its launch shape: lets a caller (bench, tests) state which
  * configuration it timed or checked.  `kernel` is the demangled name rocprofv3
  * reports, e.g. "rt::path_trace_kernel<3, 6, false, true, 4>". */
 typedef struct rt_launch_info {
@@ -316,6 +316,64 @@ int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, uint64_t n, uint32_t flags, r
  * on `hip_stream` (a hipStream_t, NULL = the null stream).  No host sync. */
 int rt_trace_rays_async(rt_ctx* ctx, const rt_ray* rays_dev, uint64_t n, uint32_t flags,
                         rt_ray_hit* hits_dev, void* hip_stream);
+
+/* ---- first-hit feature buffers ----------------------------------------------
+ * What each pixel sees: for sample index n in
+ * [sample_base, sample_base + spp) the camera ray of rt_render's sample n of
+ * that pixel (seed + n, Halton dimensions 0 and 1, generateCameraRay) and its
+ * closest hit (t, id) exactly as bounce 0 of the render finds it.  Per sample
+ * a hit gives a = material.diffuse.xyz of primitive id (a light: its diffuse,
+ * not its emissive), N = the triangle's unflipped unit normal
+ * normalize(cross(e1, e2)) or the sphere's normalize(hit point - centre),
+ * t, and h = 1; a miss gives zero for all four.  The sums run in fp32 in
+ * ascending n from +0 and are divided by (float)spp:
+ *   albedo        4 floats per pixel: (sum a.r, sum a.g, sum a.b, sum h) / spp;
+ *                 the fourth is the coverage
+ *   normal_depth  4 floats per pixel: (sum N.x, sum N.y, sum N.z, sum t) / spp;
+ *                 depth / coverage is the mean t over the hits
+ *   first_hit     (t, id) of sample n = sample_base; a miss is (1000.0f, -1),
+ *                 the render's tmax bit for bit, as rt_trace_rays reports it
+ * RT_AOV_CENTER: one ray through every pixel centre (jitter 0.5, 0.5), the
+ * picking / id-buffer form: spp must be 1, sample_base is ignored and no seeds
+ * are needed.
+ *
+ * These entry points were added without a change of RTPT_ABI_VERSION (nothing
+ * else changed): a caller that may meet an older library detects the feature
+ * by the presence of the symbol rt_render_aov (dlsym). */
+#define RT_AOV_CENTER 0x400u
+
+typedef struct rt_aov_params {
+    uint32_t spp;         /* 1 .. 2^24 (the coverage sum stays exact)            */
+    uint32_t sample_base;
+    uint32_t row_start;   /* rows as in rt_render_params                         */
+    uint32_t row_step;
+    uint32_t row_count;
+    uint32_t flags;       /* RT_OUT_DEVICE, RT_AOV_CENTER                        */
+} rt_aov_params; /* 24 B */
+
+typedef struct rt_aov_buffers {
+    float* albedo;          /* row_count * W * 4 floats, or NULL                 */
+    float* normal_depth;    /* row_count * W * 4 floats, or NULL                 */
+    rt_ray_hit* first_hit;  /* row_count * W entries, or NULL                    */
+} rt_aov_buffers; /* 24 B */
+
+/* Render the feature buffers and block until done.  Any subset of the three
+ * buffers may be NULL, but not all.  With RT_OUT_DEVICE every non-NULL buffer
+ * is device memory, otherwise host memory (the context's staging buffers carry
+ * them).  RT_ERR_INVALID_ARG: a NULL context, params or buffers, all three
+ * buffers NULL, spp == 0 or spp > 2^24, RT_AOV_CENTER with spp != 1, an
+ * unknown flag bit, a bad row partition.  RT_ERR_STATE: a jittered call before
+ * seeds are set.  rt_last_launch then names the instantiation, e.g.
+ * "rt::aov_kernel<6, false, true>" (layout, spheres, fixed-digit Halton) at
+ * one lane per pixel, and rt_last_kernel_ms gives its device time.  The
+ * context's lanes_per_pixel and walk_scheduler options are ignored. */
+int rt_render_aov(rt_ctx* ctx, const rt_aov_params* params, const rt_aov_buffers* buffers);
+
+/* Asynchronous variant: every non-NULL buffer is device memory, the kernel is
+ * enqueued on `hip_stream` (a hipStream_t, NULL = the null stream).  No host
+ * sync. */
+int rt_render_aov_async(rt_ctx* ctx, const rt_aov_params* params, const rt_aov_buffers* buffers_dev,
+                        void* hip_stream);
 
 /* The exactness domain of a scene (host-only, no device): a ray is in it when
  * all eight floats are finite, max |origin component| <= origin_max,

@@ -2,14 +2,15 @@
 # Device-code identity of the working tree against a git revision (no GPU
 # needed): the gate of a refactor that must not change an instruction.
 #   tools/isa_diff.sh <git-rev>
-# Each of the five .hip files is compiled to gfx950 assembly with the
+# Each .hip file that <git-rev> has too is compiled to gfx950 assembly with the
 # Makefile's HIPFLAGS, once from the working tree and once from a temporary
 # git worktree of <rev> (removed afterwards), and the two .s files are
 # compared byte for byte.  Both sides get the same -cuid=: by default hipcc
 # derives the compilation-unit id (the __hip_cuid_* symbol) from the source
 # path, the only path-dependent text in the assembly.  One line per
 # file: identical (with the sha256 of the .s), or the symbol that holds the
-# first difference.  Exit status 1 on any difference.  rt_kernel.hip takes
+# first difference; a file the revision lacks is reported as new.  Exit
+# status 1 on any difference.  rt_kernel.hip takes
 # minutes per compile; the ten compiles run ISA_JOBS (default 4) at a time.
 set -eu
 [ $# -eq 1 ] || { echo "usage: $0 <git-rev>" >&2; exit 2; }
@@ -18,18 +19,20 @@ T=$(mktemp -d)
 trap 'git -C "$R" worktree remove --force "$T/rev" >/dev/null 2>&1 || true; rm -rf "$T"' EXIT
 git -C "$R" worktree add --detach "$T/rev" "$1" >/dev/null
 CC=$(make -s -C "$R" --eval 'isa-cc: ; @echo $(HIPCC) $(HIPFLAGS)' isa-cc)
-FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah"
+FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_aov"
 mkdir -p "$T/new" "$T/old"
 export T CC
 for f in $FILES; do
     echo "new $f $R"
     echo "old $f $T/rev"
 done | xargs -P "${ISA_JOBS:-4}" -L 1 bash -c \
-    'cd "$3" && $CC --offload-device-only -S -cuid=isa_diff gpuraytracer_amd/csrc/$2.hip -o "$T/$1/$2.s" 2>"$T/$1/$2.err" ||
+    'cd "$3" && { [ -f gpuraytracer_amd/csrc/$2.hip ] || exit 0; } && $CC --offload-device-only -S -cuid=isa_diff gpuraytracer_amd/csrc/$2.hip -o "$T/$1/$2.s" 2>"$T/$1/$2.err" ||
          { cat "$T/$1/$2.err" >&2; exit 255; }' _
 rc=0
 for f in $FILES; do
-    if cmp -s "$T/new/$f.s" "$T/old/$f.s"; then
+    if [ ! -f "$T/old/$f.s" ]; then  # a file <git-rev> does not have: nothing to compare
+        echo "$f.hip: new (sha256 $(sha256sum <"$T/new/$f.s" | cut -d' ' -f1))"
+    elif cmp -s "$T/new/$f.s" "$T/old/$f.s"; then
         echo "$f.hip: identical (sha256 $(sha256sum <"$T/new/$f.s" | cut -d' ' -f1))"
     else
         # the last symbol label (name: in column 0, not a local .L label) at or before the first differing line
