@@ -133,6 +133,16 @@ class BuildStats(ctypes.Structure):  # rt_build_stats
                 ("tri_bvh_temp_kib", ctypes.c_uint32)]
 
 
+class TriBvhDump(ctypes.Structure):  # rt_tri_bvh_dump
+    _fields_ = [("n_triangles", ctypes.c_uint32), ("nodes_per_layout", ctypes.c_uint32),
+                ("leaf_max", ctypes.c_uint32), ("margin", ctypes.c_float),
+                ("nodes", ctypes.c_void_p), ("sorted", ctypes.c_void_p),
+                ("perm", ctypes.c_void_p), ("isect", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(TriBvhDump) == 48
+
+
 class TileLayout(ctypes.Structure):  # rt_tile_layout_info
     _fields_ = [("rows", ctypes.c_uint32), ("rows_max", ctypes.c_uint32),
                 ("row_bytes", ctypes.c_uint64), ("tile_bytes", ctypes.c_uint64)]
@@ -192,6 +202,9 @@ SIGNATURES = {
     "rt_destroy": (ctypes.c_int, [_P]),
     "rt_last_launch": (ctypes.c_int, [_P, ctypes.POINTER(LaunchInfo)]),
     "rt_build_info": (ctypes.c_int, [_P, ctypes.POINTER(BuildStats)]),
+    "rt_debug_tri_bvh": (ctypes.c_int, [_P, ctypes.POINTER(TriBvhDump)]),
+    "rt_debug_tri_bvh_host": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(CreateOptions),
+                                             ctypes.POINTER(TriBvhDump)]),
     "rt_math_selfcheck": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rt_comm_unique_id": (ctypes.c_int, [_P]),
     "rt_comm_init": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P]),

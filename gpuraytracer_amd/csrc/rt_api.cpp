@@ -54,6 +54,7 @@ struct rt_ctx {
     bool sph_compact = false;        // rt_scene.hpp sphere_compact_usable: the sphere kernel's tables exist
     uint64_t light_mask = 0;         // rt_scene.hpp light_mask: the box-cluster kernel's light flags
     uint32_t tri_bvh_build_used = 0; // rt_tri_bvh_build of the built tree (0: none)
+    uint32_t tri_leaf_max = 1;       // triangles per leaf at most in the built tree (rt_debug_tri_bvh)
     float tri_bvh_build_ms = 0.0f;   // wall time of the triangle-BVH build
     size_t tri_bvh_temp_bytes = 0;   // peak temporaries of the GPU SAH build
     float scene_compile_ms = 0.0f;   // host scene compile (rt_scene.cpp compile_scene)
@@ -967,6 +968,8 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
                 c->tri_bvh_nodes = (uint32_t)(nodes.size() / (4 * rt::kTriCompactLayouts));
             }
             if (c->tri_build == RT_TRI_BVH_GPU_LBVH) c->tri_bvh_nodes = (uint32_t)nn;
+            // the LBVH leaves hold one triangle; the SAH builds clamp the option to 1..128
+            c->tri_leaf_max = c->tri_build == RT_TRI_BVH_GPU_LBVH ? 1u : std::min(128u, std::max(1u, ro.tri_leaf_max));
             c->tri_bvh_build_used = c->tri_build;
             c->tri_bvh_build_ms = std::chrono::duration<float, std::milli>(clk::now() - t_build).count();
         }
@@ -1191,6 +1194,57 @@ int rt_build_info(const rt_ctx* c, rt_build_stats* info) {
     info->tri_bvh_build_ms = c->tri_bvh_build_ms;
     info->scene_compile_ms = c->scene_compile_ms;
     info->tri_bvh_temp_kib = (uint32_t)((c->tri_bvh_temp_bytes + 1023) / 1024);
+    return RT_OK;
+}
+
+int rt_debug_tri_bvh(const rt_ctx* c, rt_tri_bvh_dump* dump) {
+    if (!c || !dump) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (!c->tri_bvh_build_used || !c->d_tri_nodes) return RT_ERR_STATE;
+    const size_t nT = c->scene.tri_isect.size(), nn = c->tri_bvh_nodes;
+    dump->n_triangles = (uint32_t)nT;
+    dump->nodes_per_layout = (uint32_t)nn;
+    dump->leaf_max = c->tri_leaf_max;
+    dump->margin = c->scene.margin;
+    DeviceGuard g(c->device);
+    const struct { void* dst; const void* src; size_t bytes; } copies[4] = {
+        {dump->nodes, c->d_tri_nodes, rt::kTriCompactLayouts * nn * sizeof(uint4)},
+        {dump->sorted, c->d_tri_sorted, nT * sizeof(rt::TriIsect)},
+        {dump->perm, c->d_tri_perm, nT * sizeof(uint32_t)},
+        {dump->isect, c->d_tri_isect, nT * sizeof(rt::TriIsect)}};
+    for (const auto& cp : copies) {
+        if (!cp.dst) continue;
+        const hipError_t e = hipMemcpy(cp.dst, cp.src, cp.bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return RT_ERR_LAUNCH;
+    }
+    return RT_OK;
+}
+
+int rt_debug_tri_bvh_host(const rt_scene_desc* d, const rt_create_options* opt, rt_tri_bvh_dump* dump) {
+    if (!d || !dump || !d->camera || !d->square_lights) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    Resolved ro;
+    const char* why = nullptr;
+    if (!resolve_options(opt, &ro, &why)) return fail(nullptr, RT_ERR_INVALID_ARG, why);
+    rt::CompiledScene s;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0],
+                           d->spheres, d->n_spheres, &s, &err, ro.build))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    const size_t nT = s.tri_isect.size();
+    dump->n_triangles = (uint32_t)nT;
+    dump->nodes_per_layout = 0;
+    dump->leaf_max = std::min(128u, std::max(1u, ro.tri_leaf_max));
+    dump->margin = s.margin;
+    if (nT == 0) return fail(nullptr, RT_ERR_INVALID_ARG, "the scene has no triangles");
+    if (dump->isect) memcpy(dump->isect, s.tri_isect.data(), nT * sizeof(rt::TriIsect));
+    if (!dump->nodes && !dump->sorted && !dump->perm) return RT_OK;  // sizes only: no build
+    std::vector<uint32_t> nodes, perm;
+    std::vector<rt::TriIsect> sorted;
+    if (!rt::build_tri_sah(s.tri_isect, s.margin, &nodes, &sorted, &perm, ro.tri_leaf_max, ro.tri_leaf_cost))
+        return fail(nullptr, RT_ERR_INVALID_ARG, "triangle BVH build: too many triangles (2^24)");
+    dump->nodes_per_layout = (uint32_t)(nodes.size() / (4 * rt::kTriCompactLayouts));
+    if (dump->nodes) memcpy(dump->nodes, nodes.data(), nodes.size() * sizeof(uint32_t));
+    if (dump->sorted) memcpy(dump->sorted, sorted.data(), nT * sizeof(rt::TriIsect));
+    if (dump->perm) memcpy(dump->perm, perm.data(), nT * sizeof(uint32_t));
     return RT_OK;
 }
 

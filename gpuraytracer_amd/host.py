@@ -22,7 +22,7 @@ from ._native import (LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
                       RenderParamsC,
-                      RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, float3,
+                      RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, float3,
                       lib)
 
 DEFAULT_SEED_KEY = 0x5EED00000000
@@ -88,6 +88,23 @@ def place_tiles_host(gathered: np.ndarray, width: int, height: int, world: int) 
     _check(lib.rt_place_tiles_host(g.ctypes.data_as(ctypes.c_void_p), width, height, world,
                                    _pixel_flags(fp16, rgba8), frame.ctypes.data_as(ctypes.c_void_p)))
     return frame
+
+
+def _tri_bvh_dump(call, n: int, nodes_cap: int) -> dict:
+    """Run ``call(dump)`` with buffers for ``n`` triangles and ``nodes_cap``
+    nodes per layout; the rt_tri_bvh_dump as a dict of numpy arrays."""
+    nodes = np.zeros((8 * nodes_cap, 4), np.uint32)
+    srt = np.zeros((n, 12), np.float32)
+    perm = np.zeros(n, np.uint32)
+    isect = np.zeros((n, 12), np.float32)
+    d = TriBvhDump()
+    d.nodes, d.sorted, d.perm, d.isect = (a.ctypes.data for a in (nodes, srt, perm, isect))
+    call(d)
+    total = int(d.nodes_per_layout)
+    assert int(d.n_triangles) == n and total <= nodes_cap
+    return {"n_triangles": n, "nodes_per_layout": total, "leaf_max": int(d.leaf_max),
+            "margin": np.float32(d.margin), "nodes": nodes[:8 * total].reshape(8, total, 4).copy(),
+            "sorted": srt, "perm": perm, "isect": isect}
 
 
 @dataclass
@@ -297,6 +314,17 @@ class Scene:
         rec = (ctypes.c_float * (16 * n))()
         _check(lib.rt_debug_light_mask(ctypes.byref(self.desc()), ctypes.byref(mask), rec, n))
         return int(mask.value), np.frombuffer(rec, np.float32).reshape(-1, 16).copy()
+
+    def tri_bvh_host(self, options: "Options | None" = None) -> dict:
+        """The triangle BVH of the host binned-SAH build for this scene
+        (rt_debug_tri_bvh_host; no device), as ``Renderer.tri_bvh`` returns a
+        context's: what a ``tri_build="host"`` context with these options
+        uploads.  Built at any triangle count >= 1."""
+        n = self.n_triangles
+        opt = None if options is None else ctypes.byref(options.c())
+        desc = self.desc()
+        return _tri_bvh_dump(lambda d: _check(lib.rt_debug_tri_bvh_host(ctypes.byref(desc), opt, ctypes.byref(d))),
+                             n, max(2 * n - 1, 1))
 
     def ray_domain(self) -> dict:
         """The exactness domain of ``Renderer.trace_rays`` for this scene
@@ -676,6 +704,19 @@ class Renderer:
         b = BuildStats()
         _check(lib.rt_build_info(self._ctx, ctypes.byref(b)), self._ctx)
         return {k: getattr(b, k) for k, _ in BuildStats._fields_}
+
+    def tri_bvh(self) -> dict:
+        """The context's triangle BVH as the walks read it (rt_debug_tri_bvh),
+        copied to the host: ``nodes`` (8, nodes_per_layout, 4) uint32 -- per
+        octant layout the entries of three fp16 near/far words and an escape
+        or leaf word --, ``sorted`` (n, 12) float32 records in leaf order,
+        ``perm`` (n,) uint32 leaf order -> id, ``isect`` (n, 12) float32 records
+        in id order, and ``n_triangles``, ``nodes_per_layout``, ``margin``,
+        ``leaf_max``.  RtError (RT_ERR_STATE) when the context built none."""
+        sizes = TriBvhDump()
+        _check(lib.rt_debug_tri_bvh(self._ctx, ctypes.byref(sizes)), self._ctx)
+        return _tri_bvh_dump(lambda d: _check(lib.rt_debug_tri_bvh(self._ctx, ctypes.byref(d)), self._ctx),
+                             int(sizes.n_triangles), int(sizes.nodes_per_layout))
 
     def last_kernel_ms(self) -> float:
         ms = ctypes.c_float()

@@ -400,6 +400,47 @@ typedef struct rt_build_stats {
 } rt_build_stats;
 int rt_build_info(const rt_ctx* ctx, rt_build_stats* info);
 
+/* Debug: the triangle BVH as the walks read it, copied to
+ * host memory for a node-by-node check of a build (tests/tri_bvh_tree.py).
+ * The four counts and the margin are always written; each non-NULL buffer is
+ * filled, so a first call with NULL buffers gives the sizes:
+ *   nodes   8 * nodes_per_layout entries of 4 uint32: layout o of octant o at
+ *           entry o * nodes_per_layout; three words of fp16 near/far planes,
+ *           then escape | 2^31 (an entry index over all 8 layouts) or a leaf
+ *           word first | (count - 1) << 24
+ *   sorted  n_triangles intersection records of 12 floats, in leaf order
+ *   perm    n_triangles ids: leaf order -> triangle id
+ *   isect   n_triangles intersection records of 12 floats, in id order
+ * margin is the culling margin every box was padded by before it was rounded
+ * outward to fp16, leaf_max the most triangles a leaf of this build may hold
+ * (tri_leaf_max as resolved; 1 for the LBVH).
+ *
+ * These entry points were added without a change of RTPT_ABI_VERSION: a caller
+ * detects them by the presence of the symbol rt_debug_tri_bvh (dlsym). */
+typedef struct rt_tri_bvh_dump {
+    uint32_t n_triangles;
+    uint32_t nodes_per_layout;
+    uint32_t leaf_max;
+    float margin;
+    uint32_t* nodes;
+    float* sorted;
+    uint32_t* perm;
+    float* isect;
+} rt_tri_bvh_dump; /* 48 B */
+
+/* The tree of a context, whichever build made it (host-side copies of the
+ * device arrays; no kernel runs).  RT_ERR_STATE when the context built no
+ * triangle BVH. */
+int rt_debug_tri_bvh(const rt_ctx* ctx, rt_tri_bvh_dump* dump);
+
+/* The same dump from the scene compile and the host binned-SAH build alone
+ * (host-only, no device): what a context created with RT_TRI_BVH_HOST_SAH and
+ * these options uploads.  The tree is built at any triangle count >= 1,
+ * whatever layout rt_create would choose.  nodes_per_layout is known only
+ * after the build and is at most 2 * n_triangles - 1: a caller sizes `nodes`
+ * for that bound to get the tree in one call. */
+int rt_debug_tri_bvh_host(const rt_scene_desc* scene, const rt_create_options* opt, rt_tri_bvh_dump* dump);
+
 /* Self-check of the kernels' short correctly rounded sqrt and reciprocal
  *  against the IEEE expansions on every one of the 2^32 float
  * bit patterns, on the current device: mismatches[0] sqrt, [1] reciprocal

@@ -18,6 +18,8 @@ Sets (every scene lies inside [-2.5, 2.5]^3):
      with +0 and -0 components, origins inside spheres and tangent rays
   E  rays outside the exactness domain mixed into waves of
      in-domain rays, and one block of 64 consecutive ones
+  G  rays grazing the box faces of every triangle (tests/test_tri_bvh_tree.py,
+     tests/test_gpu_tri_bvh_tree.py)
 """
 import functools
 
@@ -274,6 +276,42 @@ def set_e(B, dom):
     mixed[512:576] = True
     r[mixed] = out[mixed]
     return r
+
+
+# ---- set G -------------------------------------------------------------------
+
+G_INSET = f32(2.0 ** -10)
+
+
+def set_g(scene, seed=9):
+    """(rays, target): rays that graze the faces of the triangles' boxes, six a
+    triangle.  For each triangle k and axis a: p = v + 2^-10 (c - v), v the
+    triangle's extreme vertex on a (the highest for even k + a, else the
+    lowest) and c its centroid; two rays through p whose direction has
+    component +0 and -0 on a and a random angle in the other two axes, origin
+    p - 0.5 d, tmin 0.001, tmax 1000.  Such a ray runs parallel to the box face
+    next to v at 2^-10 of the triangle's size from it: a box that is short by
+    an fp16 step there (1e-3 at |x| in [2, 4)) loses the hit.  target[j] is the
+    triangle ray j aims at."""
+    rng = np.random.default_rng(seed)
+    v = _tri_vertices(scene)
+    n = len(v)
+    c = (v[:, 0] + v[:, 1] + v[:, 2]) / f32(3.0)
+    rows, target = [], []
+    for a in range(3):
+        high = (np.arange(n) + a) % 2 == 0
+        pick = np.where(high, np.argmax(v[:, :, a], 1), np.argmin(v[:, :, a], 1))
+        ext = v[np.arange(n), pick]
+        p = ext + G_INSET * (c - ext)
+        th = rng.uniform(0.0, 2.0 * np.pi, n)
+        for zero in (0.0, -0.0):
+            d = np.empty((n, 3), f32)
+            d[:, a] = f32(zero)
+            d[:, (a + 1) % 3] = np.cos(th).astype(f32)
+            d[:, (a + 2) % 3] = np.sin(th).astype(f32)
+            rows.append(pack(p - f32(0.5) * d, d, f32(0.001), f32(1000.0)))
+            target.append(np.arange(n))
+    return np.concatenate(rows), np.concatenate(target).astype(np.int32)
 
 
 # ---- rays in the plane of an oblique face ---------------------------------------

@@ -474,11 +474,12 @@ def test_gpu_sah_1m_triangles_bounded_temporaries():
     assert np.array_equal(gpu.view(np.uint32), host.view(np.uint32))
 
 
-@pytest.mark.parametrize("build", ["gpusah", "host"])
+@pytest.mark.parametrize("build", ["gpusah", "host", "lbvh"])
 def test_triangle_bvh_coincident_centroids(build):
     """600 copies of one small triangle (every centroid in one point: the SAH
-    builds split such a node by index) plus the room: bit-exact, ties to the
-    lower id, and the GPU build reports 2n - 1 nodes."""
+    builds split such a node by index, the LBVH by the index tie-break of
+    equal Morton codes) plus the room: bit-exact, ties to the lower id, and
+    the GPU build reports 2n - 1 nodes."""
     base = Scene.cornell_box(40, 24)
     n = 36 + 600
     mats = (MaterialGPU * n)()

@@ -5,7 +5,15 @@ layout, escapes inside the layout, every box a superset of its subtree and of
 its triangles padded by the margin, and the stackless closest-hit walk of each
 octant layout equal to brute force on 4000 random rays (exact duplicates
 included: ties to the lower id).  The GPU walks over the same layout are the
-parity tests (tests/test_gpu_parity.py::test_triangle_bvh_gpu_build_bit_exact)."""
+parity tests (tests/test_gpu_parity.py::test_triangle_bvh_gpu_build_bit_exact).
+
+The same invariants, and more (a proper preorder binary tree, the eight
+layouts one tree with reversed child order, near/far slots), are checked in
+numpy by tests/tri_bvh_tree.py on a dump of the tree
+(``Scene.tri_bvh_host`` / ``Renderer.tri_bvh``): tests/test_tri_bvh_tree.py
+for this host build on the inputs that break builders (tests/tri_bvh_scenes.py)
+with negative controls of the checker, tests/test_gpu_tri_bvh_tree.py for the
+trees of the two GPU builders (rt_lbvh.hip, rt_gsah.hip)."""
 import os
 import shutil
 import subprocess
