@@ -11,7 +11,8 @@ reference's Swift host API, used by the tests and ``bench.py``:
   the seed texture, ``draw`` dispatches and waits); ``trace_rays`` answers
   batches of the caller's own rays (closest hit / any hit) through the same
   acceleration structures; ``render_aov`` gives the first-hit feature buffers
-  (albedo, normal, depth, coverage, primitive id) of the beauty samples.
+  (albedo, normal, depth, coverage, primitive id) of the beauty samples;
+  ``denoise`` / ``render_denoised`` filter a low-spp render with them.
 
 There is no CPU fallback: importing fails loudly when ``librtpt.so`` has not
 been built (``make`` or ``__graft_entry__.build()``), and rendering fails
@@ -19,8 +20,8 @@ loudly without a HIP device.
 """
 from __future__ import annotations
 
-from ._native import (ABI_VERSION, RT_AOV_CENTER, RT_RAYS_CHUNK, AovBuffers, AovParams, CameraGPU, MaterialGPU, RtError, SphereGPU,
-                      SquareLightGPU, float3, lib, library_path)
+from ._native import (ABI_VERSION, RT_AOV_CENTER, RT_RAYS_CHUNK, AovBuffers, AovParams, CameraGPU, DenoiseBuffers,
+                      DenoiseParams, MaterialGPU, RtError, SphereGPU, SquareLightGPU, float3, lib, library_path)
 from .host import (DEFAULT_SEED_KEY, MisParams, Options, RenderParams, Renderer, Scene, comm_unique_id,
                    place_tiles_host, seed_splitmix, tile_layout, tonemap_rgba8)
 
@@ -29,4 +30,5 @@ __all__ = [
     "RtError", "lib", "library_path", "Scene", "Renderer", "RenderParams", "MisParams",
     "DEFAULT_SEED_KEY", "seed_splitmix", "tonemap_rgba8", "comm_unique_id", "tile_layout",
     "place_tiles_host", "RT_RAYS_CHUNK", "RT_AOV_CENTER", "AovParams", "AovBuffers",
+    "DenoiseParams", "DenoiseBuffers",
 ]

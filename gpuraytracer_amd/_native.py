@@ -177,6 +177,19 @@ class AovBuffers(ctypes.Structure):  # rt_aov_buffers
 assert ctypes.sizeof(AovParams) == 24 and ctypes.sizeof(AovBuffers) == 24
 
 
+class DenoiseParams(ctypes.Structure):  # rt_denoise_params
+    _fields_ = [("iterations", ctypes.c_uint32), ("normal_power_log2", ctypes.c_uint32),
+                ("sigma_luminance", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+                ("depth_floor", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class DenoiseBuffers(ctypes.Structure):  # rt_denoise_buffers
+    _fields_ = [(n, ctypes.c_void_p) for n in ("color_a", "color_b", "albedo", "normal_depth", "out")]
+
+
+assert ctypes.sizeof(DenoiseParams) == 32 and ctypes.sizeof(DenoiseBuffers) == 40 and DenoiseBuffers.out.offset == 32
+
+
 class MisParamsC(ctypes.Structure):  # rt_mis_params
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("camera_rays", "mis_samples", "row_start", "row_step", "row_count", "flags")]
@@ -197,6 +210,9 @@ SIGNATURES = {
     "rt_trace_rays_async": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "rt_render_aov": (ctypes.c_int, [_P, ctypes.POINTER(AovParams), ctypes.POINTER(AovBuffers)]),
     "rt_render_aov_async": (ctypes.c_int, [_P, ctypes.POINTER(AovParams), ctypes.POINTER(AovBuffers), _P]),
+    "rt_denoise_params_default": (None, [ctypes.POINTER(DenoiseParams)]),
+    "rt_denoise": (ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers)]),
+    "rt_denoise_async": (ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers), _P]),
     "rt_debug_ray_domain": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(RayDomainInfo)]),
     "rt_last_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_destroy": (ctypes.c_int, [_P]),

@@ -69,6 +69,8 @@ struct rt_ctx {
     size_t hits_cap = 0;
     void* d_aov[3] = {nullptr, nullptr, nullptr};  // staging for host feature buffers (rt_render_aov)
     size_t aov_cap[3] = {0, 0, 0};
+    void* d_den[6] = {};           // rt_denoise: the (D, V) ping-pong, then staging for the four host inputs
+    size_t den_cap[6] = {};
     void* d_mis_part = nullptr;    // per-ray MIS results of a split launch (rt_mis.hip)
     size_t mis_part_cap = 0;
     uint32_t* d_seeds = nullptr;
@@ -214,6 +216,7 @@ void release(rt_ctx* c) {
     (void)hipFree(c->d_rays);
     (void)hipFree(c->d_hits);
     for (void* b : c->d_aov) (void)hipFree(b);
+    for (void* b : c->d_den) (void)hipFree(b);
     (void)hipFree(c->d_seeds);
     (void)hipFree(c->d_sum);
     (void)hipFree(c->d_out);
@@ -767,6 +770,75 @@ int render_aov_impl(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b, 
     return RT_OK;
 }
 
+// rt_denoise / rt_denoise_async: prepare, variance pre-filter and the a-trous
+// passes (rt_denoise.hip) on whole frames.  Host buffers go through the
+// context's staging buffers on its own stream; the staged output is the staged
+// color_a (the filter may write over it).
+int denoise_impl(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buffers* b, bool dev, hipStream_t stream,
+                 bool sync) {
+    static_assert(sizeof(rt_denoise_params) == 32 && sizeof(rt_denoise_buffers) == 40 &&
+                      offsetof(rt_denoise_buffers, out) == 32,
+                  "rt_denoise_params / rt_denoise_buffers layout");
+    if (!p) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: params is null");
+    if (!b) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: buffers is null");
+    const void* in[4] = {b->color_a, b->color_b, b->albedo, b->normal_depth};
+    static const char* const names[4] = {"color_a", "color_b", "albedo", "normal_depth"};
+    for (int k = 0; k < 4; ++k)
+        if (!in[k]) return fail(c, RT_ERR_INVALID_ARG, std::string("rt_denoise: ") + names[k] + " is null");
+    if (!b->out) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: out is null");
+    if (p->iterations < 1 || p->iterations > 6)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: iterations must be in [1, 6]");
+    if (p->normal_power_log2 > 10) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: normal_power_log2 must be <= 10");
+    if (!(p->sigma_luminance >= 0.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: sigma_luminance must be >= 0");
+    if (!(p->sigma_depth >= 0.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: sigma_depth must be >= 0");
+    if (!(p->depth_floor > 0.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: depth_floor must be > 0");
+    if (p->flags & ~(uint32_t)RT_OUT_DEVICE) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: unknown flag bits");
+    if (p->reserved[0] || p->reserved[1]) return fail(c, RT_ERR_INVALID_ARG, "rt_denoise: reserved must be 0");
+
+    const size_t bytes = (size_t)c->scene.cam.W * (size_t)c->scene.cam.H * sizeof(float4);
+    int st;
+    for (int k = 0; k < (dev ? 2 : 6); ++k)
+        if ((st = ensure_staging(c, &c->d_den[k], &c->den_cap[k], bytes, "hipMalloc(denoise scratch)")) != RT_OK)
+            return st;
+    hipError_t e;
+    const void* kin[4] = {in[0], in[1], in[2], in[3]};
+    void* kout = b->out;
+    if (!dev) {
+        for (int k = 0; k < 4; ++k) {
+            if ((e = hipMemcpyAsync(c->d_den[2 + k], in[k], bytes, hipMemcpyHostToDevice, stream)) != hipSuccess)
+                return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(denoise inputs)", e);
+            kin[k] = c->d_den[2 + k];
+        }
+        kout = c->d_den[2];
+    }
+    rt::DenoiseParams K{};
+    K.color_a = static_cast<const float4*>(kin[0]);
+    K.color_b = static_cast<const float4*>(kin[1]);
+    K.albedo = static_cast<const float4*>(kin[2]);
+    K.normal_depth = static_cast<const float4*>(kin[3]);
+    K.out = static_cast<float4*>(kout);
+    K.scratch[0] = static_cast<float4*>(c->d_den[0]);
+    K.scratch[1] = static_cast<float4*>(c->d_den[1]);
+    K.W = c->scene.cam.W;
+    K.H = c->scene.cam.H;
+    K.iterations = p->iterations;
+    K.normal_power_log2 = p->normal_power_log2;
+    K.sigma_luminance = p->sigma_luminance;
+    K.sigma_depth = p->sigma_depth;
+    K.depth_floor = p->depth_floor;
+    (void)hipEventRecord(c->ev0, stream);
+    if ((e = rt::launch_denoise(K, stream, &c->launch)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "denoise launch", e);
+    c->launched = true;
+    (void)hipEventRecord(c->ev1, stream);
+    c->timed = true;
+    if (!dev && (e = hipMemcpyAsync(b->out, kout, bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(denoise out)", e);
+    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "denoise execution", e);
+    return RT_OK;
+}
+
 // rt_create_options (include/rtpt.h) -> the context's choices and the host
 // builds' options.  False (with *why) for a value outside its range.
 struct Resolved {
@@ -1055,6 +1127,28 @@ int rt_render_aov_async(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers*
     if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
     DeviceGuard g(c->device);
     return render_aov_impl(c, p, b_dev, true, (hipStream_t)hip_stream, false);
+}
+
+void rt_denoise_params_default(rt_denoise_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->iterations = 5;
+    p->normal_power_log2 = 7;
+    p->sigma_luminance = 4.0f;
+    p->sigma_depth = 1.0f;
+    p->depth_floor = 0.01f;
+}
+
+int rt_denoise(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buffers* b) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return denoise_impl(c, p, b, p && (p->flags & RT_OUT_DEVICE), c->stream, true);
+}
+
+int rt_denoise_async(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buffers* b_dev, void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return denoise_impl(c, p, b_dev, true, (hipStream_t)hip_stream, false);
 }
 
 int rt_debug_ray_domain(const rt_scene_desc* d, rt_ray_domain_info* info) {

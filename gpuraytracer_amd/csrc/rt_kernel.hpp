@@ -304,6 +304,36 @@ struct AovParams {
 };
 hipError_t launch_aov(const AovParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info);
 
+// ---- a-trous denoiser (rt_denoise.hip; include/rtpt.h rt_denoise) -----------
+// Pixels on a side of a workgroup's tile; a wave is four rows of it.
+constexpr uint32_t kDenoiseTile = 16;
+// The largest a-trous step whose footprint a workgroup stages in LDS (0: none);
+// larger steps read global memory.  Measured: profiles/r16/denoise.md.
+#ifndef RT_DENOISE_LDS_MAX_STEP
+#define RT_DENOISE_LDS_MAX_STEP 4
+#endif
+static_assert(RT_DENOISE_LDS_MAX_STEP <= 8, "a step-16 footprint (80 x 80 texels of 32 B) is past the CU's 160 KiB of LDS");
+// THE dynamic LDS of an iteration workgroup at `step`: (D, V) and (N, Z) of the
+// tile and its halo of 2 * step pixels, 32 B per texel, or nothing.
+__host__ __device__ constexpr size_t denoise_lds_bytes(uint32_t step) {
+    return step <= RT_DENOISE_LDS_MAX_STEP ? (size_t)32 * (kDenoiseTile + 4 * step) * (kDenoiseTile + 4 * step)
+                                           : (size_t)0;
+}
+struct DenoiseParams {
+    const float4* color_a;       // W*H each, device memory
+    const float4* color_b;
+    const float4* albedo;
+    const float4* normal_depth;
+    float4* out;                 // may be color_a or color_b
+    float4* scratch[2];          // W*H each: the (D, V) ping-pong
+    int32_t W, H;
+    uint32_t iterations;         // 1..6
+    uint32_t normal_power_log2;  // 0..10
+    float sigma_luminance, sigma_depth, depth_floor;
+};
+// prepare, variance pre-filter, `iterations` a-trous launches; *info: the last.
+hipError_t launch_denoise(const DenoiseParams& P, hipStream_t stream, LaunchInfo* info);
+
 hipError_t launch_mis(const MisParams& P, SceneMem mem, hipStream_t stream);
 size_t mis_lds_bytes(uint32_t n_tri, uint32_t n_pairs);
 size_t mis_part_bytes(uint32_t camera_rays, size_t pixels);  // 0: no split launch

@@ -20,7 +20,7 @@ import numpy as np
 
 from ._native import (LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, TRI_BUILDS, WALKS,
-                      AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
+                      AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
                       RenderParamsC,
                       RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, float3,
                       lib)
@@ -565,6 +565,91 @@ class Renderer:
         if cur is not None:
             cur.synchronize()
         return out
+
+    def denoise(self, color_a, color_b, albedo, normal_depth, iterations: int = 5, normal_power_log2: int = 7,
+                sigma_luminance: float = 4.0, sigma_depth: float = 1.0, depth_floor: float = 0.01, out=None,
+                stream=None):
+        """Variance-guided a-trous denoiser (rt_denoise).
+        ``color_a`` / ``color_b``: renders of the first and the second half of
+        the samples, ``albedo`` / ``normal_depth``: ``render_aov`` of all of
+        them; whole frames, (H, W, 4) float32 each.  Returns the filtered
+        (H, W, 4) image: an estimate of the mean of the halves, alpha from
+        ``color_a``.
+
+        numpy arrays take the host path and block.  Contiguous float32 torch
+        tensors on the context's device take the device path, enqueued on
+        ``stream`` without a host sync (default: torch's current stream, then
+        waited for).  ``out`` (same kind and shape) may be ``color_a`` or
+        ``color_b``."""
+        p = DenoiseParams()
+        p.iterations, p.normal_power_log2 = iterations, normal_power_log2
+        p.sigma_luminance, p.sigma_depth, p.depth_floor = sigma_luminance, sigma_depth, depth_floor
+        shape = (self.scene.height, self.scene.width, 4)
+        bufs = {"color_a": color_a, "color_b": color_b, "albedo": albedo, "normal_depth": normal_depth}
+        b = DenoiseBuffers()
+        if isinstance(color_a, np.ndarray):
+            keep = []
+            for k, a in bufs.items():
+                if not isinstance(a, np.ndarray) or a.shape != shape:
+                    raise ValueError(f"{k} must be a {shape} float32 array")
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                keep.append(a)
+                setattr(b, k, a.ctypes.data)
+            res = np.empty(shape, np.float32) if out is None else out
+            if (not isinstance(res, np.ndarray) or res.dtype != np.float32 or res.shape != shape
+                    or not res.flags.c_contiguous):
+                raise ValueError(f"out must be a contiguous {shape} float32 array")
+            b.out = res.ctypes.data
+            _check(lib.rt_denoise(self._ctx, ctypes.byref(p), ctypes.byref(b)), self._ctx)
+            return res
+        import torch  # plumbing only: device memory and the caller's stream
+        res = torch.empty(shape, dtype=torch.float32, device=color_a.device) if out is None else out
+        for k, t in dict(bufs, out=res).items():
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32
+                    or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device):
+                raise ValueError(f"{k} must be a contiguous {shape} float32 tensor on the context's device")
+            setattr(b, k, t.data_ptr())
+        p.flags = RT_OUT_DEVICE
+        cur = torch.cuda.current_stream(self.device) if stream is None else None
+        handle = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        _check(lib.rt_denoise_async(self._ctx, ctypes.byref(p), ctypes.byref(b), ctypes.c_void_p(handle)), self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        return res
+
+    def render_denoised(self, params: RenderParams | None = None, return_inputs: bool = False, stream=None,
+                        **filter_args):
+        """A denoised render of ``params.spp`` samples: two renders of
+        ``spp / 2`` samples at ``sample_base`` and ``sample_base + spp / 2``,
+        the feature buffers of all ``spp`` samples, and :meth:`denoise` (its
+        keyword arguments pass through), all on device tensors and one stream
+        (default: torch's current stream), then waited for.  Returns the
+        (H, W, 4) float32 torch tensor; with ``return_inputs`` also the dict of
+        the four inputs.  Needs an even ``spp`` >= 2 and whole float32 frames."""
+        p = params or RenderParams()
+        H, W = self.scene.height, self.scene.width
+        if p.spp < 2 or p.spp % 2:
+            raise ValueError("render_denoised needs an even spp >= 2 (two halves)")
+        if p.row_start != 0 or p.row_step not in (0, 1) or p.row_count not in (0, H):
+            raise ValueError("render_denoised needs whole frames (no row partition)")
+        if p.accumulate or p.keep_sum or p.fp16 or p.rgba8:
+            raise ValueError("render_denoised renders plain float32 frames (no accumulate, keep_sum, fp16, rgba8)")
+        import torch  # plumbing only: device memory and the caller's stream
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        half = p.spp // 2
+        new = lambda: torch.empty((H, W, 4), dtype=torch.float32, device=dev)  # noqa: E731
+        inputs = {"color_a": new(), "color_b": new(), "albedo": new(), "normal_depth": new()}
+        self.render(RenderParams(spp=half, bounces=p.bounces, sample_base=p.sample_base), out=inputs["color_a"],
+                    stream=s)
+        self.render(RenderParams(spp=half, bounces=p.bounces, sample_base=p.sample_base + half),
+                    out=inputs["color_b"], stream=s)
+        self.render_aov(spp=p.spp, sample_base=p.sample_base,
+                        out={k: inputs[k] for k in ("albedo", "normal_depth")}, stream=s)
+        img = self.denoise(**inputs, stream=s, **filter_args)
+        if hasattr(s, "synchronize"):
+            s.synchronize()
+        return (img, inputs) if return_inputs else img
 
     def render_progressive(self, params: RenderParams, batch_spp: int, out, stream=None,
                            gather: bool = False):

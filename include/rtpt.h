@@ -250,8 +250,9 @@ int rt_place_tiles_host(const void* gathered, int32_t width, int32_t height, int
                         uint32_t flags, void* frame);
 
 /* Which kernel instantiation the most recent rt_render/rt_render_async,
- * rt_trace_rays/rt_trace_rays_async or rt_render_aov/rt_render_aov_async launched, with its launch shape: lets a caller (bench, tests) state which
- * configuration it timed or checked.  `kernel` is the demangled name rocprofv3
+ * rt_trace_rays/rt_trace_rays_async, rt_render_aov/rt_render_aov_async or
+ * rt_denoise/rt_denoise_async (its last pass) launched, with its launch shape:
+ * lets a caller (bench, tests) state which configuration it timed or checked.  `kernel` is the demangled name rocprofv3
  * reports, e.g. "rt::path_trace_kernel<3, 6, false, true, 4>". */
 typedef struct rt_launch_info {
     char kernel[96];
@@ -374,6 +375,69 @@ int rt_render_aov(rt_ctx* ctx, const rt_aov_params* params, const rt_aov_buffers
  * sync. */
 int rt_render_aov_async(rt_ctx* ctx, const rt_aov_params* params, const rt_aov_buffers* buffers_dev,
                         void* hip_stream);
+
+/* ---- denoiser for low-spp renders ------------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on
+ * albedo-demodulated colour.  Its edge-stopping weights come from the feature
+ * buffers of rt_render_aov (normal, depth; Schied et al. 2017); its luminance
+ * weight is scaled by a per-pixel variance estimated from two renders of half
+ * the samples each (dual buffers, Rousselle et al. 2012): render spp/2 samples
+ * at sample_base into color_a, spp/2 at sample_base + spp/2 into color_b, and
+ * rt_render_aov of all spp samples at sample_base into albedo / normal_depth.
+ * The result estimates the mean of the two halves.  The arithmetic is fixed
+ * operation by operation: the output is a function of the
+ * buffers and the parameters alone, bit for bit.  Inputs must be finite; for
+ * other inputs the result is unspecified, but no address depends on data.
+ *
+ * All five frames are whole frames of the context's camera resolution (H*W
+ * pixels of 4 floats, no row partition: a filter needs its neighbours).  No
+ * seeds are needed.  The context owns the filter's scratch (32 B per pixel),
+ * grown on first use and freed by rt_destroy; calls on one context must be
+ * ordered (one stream, or the caller's events between streams).
+ *
+ * These entry points were added without a change of RTPT_ABI_VERSION (nothing
+ * else changed): a caller that may meet an older library detects the feature
+ * by the presence of the symbol rt_denoise (dlsym). */
+typedef struct rt_denoise_params {
+    uint32_t iterations;         /* 1..6: a-trous steps 1, 2, 4, ... 2^(iterations-1) pixels  */
+    uint32_t normal_power_log2;  /* 0..10: normal weight = max(0, dot)^(2^k)                  */
+    float sigma_luminance;       /* >= 0: larger = smoother across luminance differences      */
+    float sigma_depth;           /* >= 0: tolerance along the local depth slope               */
+    float depth_floor;           /* > 0, scene units: depth difference that always passes     */
+    uint32_t flags;              /* RT_OUT_DEVICE                                             */
+    uint32_t reserved[2];        /* must be 0                                                 */
+} rt_denoise_params; /* 32 B */
+
+typedef struct rt_denoise_buffers {
+    const float* color_a;        /* H*W rgba32F: rt_render of the first half of the samples   */
+    const float* color_b;        /* H*W rgba32F: rt_render of the second half                 */
+    const float* albedo;         /* H*W*4: rt_render_aov albedo (rgb, coverage), all samples  */
+    const float* normal_depth;   /* H*W*4: rt_render_aov normal_depth                         */
+    float* out;                  /* H*W rgba32F; may alias color_a or color_b                 */
+} rt_denoise_buffers; /* 40 B */
+
+/* iterations 5, normal_power_log2 7, sigma_luminance 4.0f, sigma_depth 1.0f,
+ * depth_floor 0.01f, flags 0, reserved {0, 0}. */
+void rt_denoise_params_default(rt_denoise_params* params);
+
+/* Denoise and block until done.  The five buffers are host memory (the
+ * context's staging buffers carry them), or all device memory with
+ * RT_OUT_DEVICE.  out.a is color_a's alpha; a pixel without coverage gets the
+ * mean of the halves.  RT_ERR_INVALID_ARG, with an rt_last_error message that
+ * names the field: a NULL context, params, buffers or any of the five
+ * pointers, iterations outside 1..6, normal_power_log2 > 10, a negative or NaN
+ * sigma, depth_floor not > 0 (NaN included), an unknown flag bit, nonzero
+ * reserved.  rt_last_launch then names the last iteration's kernel, e.g.
+ * "rt::denoise_atrous_kernel<false>" (whether the workgroup staged its
+ * footprint in LDS) with its grid, block and LDS bytes, and rt_last_kernel_ms
+ * gives the device time from the first to the last launch of the call. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_buffers* buffers);
+
+/* Asynchronous variant: all five buffers are device memory, the kernels are
+ * enqueued on `hip_stream` (a hipStream_t, NULL = the null stream).  No host
+ * sync. */
+int rt_denoise_async(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_buffers* buffers_dev,
+                     void* hip_stream);
 
 /* The exactness domain of a scene (host-only, no device): a ray is in it when
  * all eight floats are finite, max |origin component| <= origin_max,
