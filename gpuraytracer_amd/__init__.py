@@ -23,12 +23,12 @@ from __future__ import annotations
 from ._native import (ABI_VERSION, RT_AOV_CENTER, RT_RAYS_CHUNK, AovBuffers, AovParams, CameraGPU, DenoiseBuffers,
                       DenoiseParams, MaterialGPU, RtError, SphereGPU, SquareLightGPU, float3, lib, library_path)
 from .host import (DEFAULT_SEED_KEY, MisParams, Options, RenderParams, Renderer, Scene, comm_unique_id,
-                   place_tiles_host, seed_splitmix, tile_layout, tonemap_rgba8)
+                   math_sums, math_values, place_tiles_host, seed_splitmix, tile_layout, tonemap_rgba8)
 
 __all__ = [
     "ABI_VERSION", "CameraGPU", "MaterialGPU", "SphereGPU", "SquareLightGPU", "float3",
     "RtError", "lib", "library_path", "Scene", "Renderer", "RenderParams", "MisParams",
     "DEFAULT_SEED_KEY", "seed_splitmix", "tonemap_rgba8", "comm_unique_id", "tile_layout",
     "place_tiles_host", "RT_RAYS_CHUNK", "RT_AOV_CENTER", "AovParams", "AovBuffers",
-    "DenoiseParams", "DenoiseBuffers",
+    "DenoiseParams", "DenoiseBuffers", "math_values", "math_sums",
 ]

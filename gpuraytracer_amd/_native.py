@@ -195,6 +195,14 @@ class MisParamsC(ctypes.Structure):  # rt_mis_params
                 ("camera_rays", "mis_samples", "row_start", "row_step", "row_count", "flags")]
 
 
+# rt_math_fn (rt_debug_math_values / rt_debug_math_sums); a Halton form carries
+# its dimension in bits 8-12
+MATH_FNS = {n: k for k, n in enumerate(
+    ("sin", "cos", "log", "exp", "pow_gamma", "sqrt", "rcp", "f2h", "h2f", "tonemap", "mis_unit",
+     "halton_loop", "halton_small", "halton_tab"))}
+RT_MATH_HOST, RT_MATH_DEVICE = 0, 1
+RT_MATH_VALUES_MAX = 1 << 24
+
 # Every entry point of include/rtpt.h: name -> (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -222,6 +230,9 @@ SIGNATURES = {
     "rt_debug_tri_bvh_host": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(CreateOptions),
                                              ctypes.POINTER(TriBvhDump)]),
     "rt_math_selfcheck": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_debug_math_values": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint64, _P]),
+    "rt_debug_math_sums": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                          ctypes.c_uint32, ctypes.c_uint32, _P]),
     "rt_comm_unique_id": (ctypes.c_int, [_P]),
     "rt_comm_init": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P]),
     "rt_render_gather": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P]),

@@ -17,12 +17,14 @@
 #include <chrono>
 #include <new>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/rtpt.h"
 #include "rt_beam.hpp"
 #include "rt_shaft.hpp"
 #include "rt_kernel.hpp"
+#include "rt_mathcheck.hpp"
 #include "rt_scene.hpp"
 
 // RT_TRI_BVH_DEFAULT resolves to this build: the GPU binned SAH builds the host
@@ -1277,6 +1279,145 @@ int rt_math_selfcheck(uint64_t* mismatches) {
     if (e != hipSuccess) return hip_fail(nullptr, RT_ERR_LAUNCH, "math_selfcheck", e);
     mismatches[0] = bad[0];
     mismatches[1] = bad[1];
+    return RT_OK;
+}
+
+namespace {
+
+// rt_debug_math_*: the x86 compile of rt::math_eval (rt_mathcheck.hpp); the
+// host's only Halton form is the reference loop.
+inline __attribute__((always_inline)) uint32_t math_eval_host(uint32_t fn, uint32_t D, uint32_t b) {
+    switch (fn) {
+        case RT_MATH_SIN: return rt::math_eval<RT_MATH_SIN>(b);
+        case RT_MATH_COS: return rt::math_eval<RT_MATH_COS>(b);
+        case RT_MATH_LOG: return rt::math_eval<RT_MATH_LOG>(b);
+        case RT_MATH_EXP: return rt::math_eval<RT_MATH_EXP>(b);
+        case RT_MATH_POW_GAMMA: return rt::math_eval<RT_MATH_POW_GAMMA>(b);
+        case RT_MATH_SQRT: return rt::math_eval<RT_MATH_SQRT>(b);
+        case RT_MATH_RCP: return rt::math_eval<RT_MATH_RCP>(b);
+        case RT_MATH_F2H: return rt::math_eval<RT_MATH_F2H>(b);
+        case RT_MATH_H2F: return rt::math_eval<RT_MATH_H2F>(b);
+        case RT_MATH_TONEMAP: return rt::math_eval<RT_MATH_TONEMAP>(b);
+        case RT_MATH_MIS_UNIT: return rt::math_eval<RT_MATH_MIS_UNIT>(b);
+        default: return rt::canon_f32(halton_host(b, D));
+    }
+}
+
+// Host side of rt_debug_math_sums: thread t of T takes the pieces t, t + T, ...
+// of the inputs (2^12 inputs a piece, so a single large chunk is shared as
+// well; a piece may span several small chunks) and adds its partial sums with
+// one atomic add per piece and chunk: sums mod 2^64, any order.
+inline __attribute__((always_inline)) void math_sum_pieces_body(uint32_t fn, uint32_t D, uint32_t first,
+                                                                uint64_t count, uint32_t chunk_log2, uint32_t t,
+                                                                uint32_t T, uint64_t* sums) {
+    constexpr uint64_t kPiece = 1ull << 12;
+    const uint64_t pieces = (count + kPiece - 1) / kPiece;
+    for (uint64_t p = t; p < pieces; p += T) {
+        const uint64_t lo = p * kPiece, hi = std::min(count, lo + kPiece);
+        for (uint64_t j = lo; j < hi;) {
+            const uint64_t c = j >> chunk_log2, end = std::min(hi, (c + 1) << chunk_log2);
+            uint64_t s0 = 0, s1 = 0;
+            for (; j < end; ++j) {
+                const uint64_t o = math_eval_host(fn, D, first + (uint32_t)j);
+                s0 += o;
+                s1 += o * (2 * (j - (c << chunk_log2)) + 1);
+            }
+            __atomic_fetch_add(&sums[2 * c], s0, __ATOMIC_RELAXED);
+            __atomic_fetch_add(&sums[2 * c + 1], s1, __ATOMIC_RELAXED);
+        }
+    }
+}
+void math_sum_pieces(uint32_t fn, uint32_t D, uint32_t first, uint64_t count, uint32_t chunk_log2, uint32_t t,
+                     uint32_t T, uint64_t* sums) {
+    math_sum_pieces_body(fn, D, first, count, chunk_log2, t, T, sums);
+}
+__attribute__((target("fma"))) void math_sum_pieces_fma(uint32_t fn, uint32_t D, uint32_t first, uint64_t count,
+                                                        uint32_t chunk_log2, uint32_t t, uint32_t T,
+                                                        uint64_t* sums) {
+    math_sum_pieces_body(fn, D, first, count, chunk_log2, t, T, sums);
+}
+
+// fn word -> (function, dimension); the checks shared by both entry points.
+// max_index: the largest input of the call (an index for the Halton forms).
+const char* math_fn_args(uint32_t fn_word, uint32_t where, uint64_t max_index, uint32_t* fn, uint32_t* D) {
+    *fn = fn_word & 0xFFu;
+    *D = (fn_word >> 8) & 0x1Fu;
+    if (where != RT_MATH_HOST && where != RT_MATH_DEVICE) return "where is neither RT_MATH_HOST nor RT_MATH_DEVICE";
+    if (*fn >= rt::kMathFnCount || (fn_word >> 13)) return "fn is not an rt_math_fn";
+    const bool halton = *fn >= RT_MATH_HALTON_LOOP;
+    if (!halton && *D) return "fn carries a dimension but is no Halton form";
+    if (*D >= 24) return "Halton dimension >= 24";
+    if (halton && *fn != RT_MATH_HALTON_LOOP) {
+        if (where == RT_MATH_HOST) return "the host has only the reference loop (RT_MATH_HALTON_LOOP)";
+        if (*fn == RT_MATH_HALTON_TAB && !rt::math_dim_has_table(*D)) return "no low-digit table for this dimension";
+        if (max_index >= rt::math_small_index_max()) return "RT_MATH_HALTON_SMALL / _TAB index >= 3^13";
+    }
+    return nullptr;
+}
+
+int math_device_ready() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(nullptr, RT_ERR_NO_DEVICE, "no HIP device");
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_debug_math_values(uint32_t fn_word, uint32_t where, const uint32_t* in_bits, uint64_t n, uint32_t* out_bits) {
+    if (n == 0) return RT_OK;
+    if (!in_bits || !out_bits) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (n > RT_MATH_VALUES_MAX) return fail(nullptr, RT_ERR_INVALID_ARG, "n > RT_MATH_VALUES_MAX");
+    uint32_t fn, D, top = 0;
+    if ((fn_word & 0xFFu) >= RT_MATH_HALTON_SMALL)  // the forms with an index bound
+        for (uint64_t j = 0; j < n; ++j) top = std::max(top, in_bits[j]);
+    if (const char* why = math_fn_args(fn_word, where, top, &fn, &D)) return fail(nullptr, RT_ERR_INVALID_ARG, why);
+    if (where == RT_MATH_HOST) {
+        for (uint64_t j = 0; j < n; ++j) out_bits[j] = math_eval_host(fn, D, in_bits[j]);
+        return RT_OK;
+    }
+    if (const int st = math_device_ready()) return st;
+    const hipError_t e = rt::math_values_device(fn, D, in_bits, (uint32_t)n, out_bits);
+    if (e != hipSuccess) return hip_fail(nullptr, RT_ERR_LAUNCH, "math_values", e);
+    return RT_OK;
+}
+
+int rt_debug_math_sums(uint32_t fn_word, uint32_t where, uint32_t first_bits, uint64_t count, uint32_t chunk_log2,
+                       uint32_t host_threads, uint64_t* sums) {
+    if (count == 0) return RT_OK;
+    if (!sums) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (chunk_log2 < rt::kMathChunkLog2Min || chunk_log2 > rt::kMathChunkLog2Max)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "chunk_log2 outside 6..31");
+    if ((uint64_t)first_bits + count > (1ull << 32))
+        return fail(nullptr, RT_ERR_INVALID_ARG, "first_bits + count > 2^32");
+    uint32_t fn, D;
+    if (const char* why = math_fn_args(fn_word, where, (uint64_t)first_bits + count - 1, &fn, &D))
+        return fail(nullptr, RT_ERR_INVALID_ARG, why);
+    const uint64_t chunk = 1ull << chunk_log2, chunks = (count + chunk - 1) >> chunk_log2;
+    if (where == RT_MATH_DEVICE) {
+        if (const int st = math_device_ready()) return st;
+        const hipError_t e = rt::math_sums_device(fn, D, first_bits, count, chunk_log2, sums);
+        if (e != hipSuccess) return hip_fail(nullptr, RT_ERR_LAUNCH, "math_sums", e);
+        return RT_OK;
+    }
+    if (host_threads < 1 || host_threads > 256) return fail(nullptr, RT_ERR_INVALID_ARG, "host_threads outside 1..256");
+    for (uint64_t c = 0; c < 2 * chunks; ++c) sums[c] = 0;
+    // fmaf is the same function with or without the FMA instructions; with
+    // them it is an instruction instead of a library call
+    const bool fma = __builtin_cpu_supports("fma");
+    auto work = [&](uint32_t t) {
+        (fma ? math_sum_pieces_fma : math_sum_pieces)(fn, D, first_bits, count, chunk_log2, t, host_threads, sums);
+    };
+    std::vector<std::thread> pool;
+    bool started = true;
+    try {
+        pool.reserve(host_threads);
+        for (uint32_t t = 1; t < host_threads; ++t) pool.emplace_back(work, t);
+    } catch (...) {  // no exception crosses the C boundary
+        started = false;
+    }
+    if (started) work(0);
+    for (auto& th : pool) th.join();
+    if (!started) return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "could not start host_threads threads");
     return RT_OK;
 }
 

@@ -18,7 +18,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from ._native import (LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
+from ._native import (MATH_FNS, RT_MATH_DEVICE, RT_MATH_HOST, RT_MATH_VALUES_MAX, LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
                       RenderParamsC,
@@ -51,6 +51,42 @@ def tonemap_rgba8(rgba32f: np.ndarray) -> np.ndarray:
     lib.rt_tonemap_rgba8(a.ctypes.data_as(ctypes.c_void_p), n,
                          out.ctypes.data_as(ctypes.c_void_p))
     return out
+
+
+def _math_fn(fn: str, dim: int, where: str) -> tuple[int, int]:
+    if fn not in MATH_FNS or where not in ("host", "device"):
+        raise ValueError(f"unknown function {fn!r} or side {where!r}")
+    return MATH_FNS[fn] | (int(dim) << 8), RT_MATH_DEVICE if where == "device" else RT_MATH_HOST
+
+
+def math_values(fn: str, in_bits, where: str = "host", dim: int = 0) -> np.ndarray:
+    """rt_debug_math_values: ``fn`` (a key of ``MATH_FNS``; ``dim`` is the
+    dimension of a Halton form) on every 32-bit input pattern of ``in_bits``,
+    by the x86 compile (``where="host"``) or by a kernel on the current device
+    (``"device"``).  Returns the result patterns (uint32, NaNs canonical)."""
+    word, side = _math_fn(fn, dim, where)
+    a = np.ascontiguousarray(in_bits, dtype=np.uint32).ravel()
+    out = np.empty(a.size, np.uint32)
+    for lo in range(0, a.size, RT_MATH_VALUES_MAX):
+        part = a[lo:lo + RT_MATH_VALUES_MAX]
+        _check(lib.rt_debug_math_values(word, side, part.ctypes.data_as(ctypes.c_void_p), part.size,
+                                        out[lo:].ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def math_sums(fn: str, first: int, count: int, chunk_log2: int = 16, where: str = "host", dim: int = 0,
+              host_threads: int = 1) -> np.ndarray:
+    """rt_debug_math_sums over the inputs ``first + j``, ``j < count``: a
+    (chunks, 2) uint64 array, per chunk of 2^chunk_log2 inputs the sum of the
+    results and the sum weighted by 2j'+1 (j' the offset in the chunk), both
+    mod 2^64."""
+    word, side = _math_fn(fn, dim, where)
+    if not 6 <= chunk_log2 <= 31 or count < 0:
+        raise ValueError("chunk_log2 outside 6..31 or a negative count")
+    sums = np.zeros(((int(count) + (1 << chunk_log2) - 1) >> chunk_log2, 2), np.uint64)
+    _check(lib.rt_debug_math_sums(word, side, first, count, chunk_log2, host_threads,
+                                  sums.ctypes.data_as(ctypes.c_void_p)))
+    return sums
 
 
 def comm_unique_id() -> bytes:

@@ -267,7 +267,7 @@ int rt_last_launch(const rt_ctx* ctx, rt_launch_info* info);
 
 /* ---- batched ray queries -------------------------------------------------
  * The exact ray queries of the render kernels (DESIGN.md §3.5, §3.6, §3.9,
- * §3.10, §3.12) for the caller's own rays, through the record layout and the
+ * §3.10, §3.24) for the caller's own rays, through the record layout and the
  * acceleration structures of the context: picking, visibility and ambient
  * occlusion between arbitrary points, line of sight, probing a scene.
  *
@@ -510,6 +510,60 @@ int rt_debug_tri_bvh_host(const rt_scene_desc* scene, const rt_create_options* o
  * bit patterns, on the current device: mismatches[0] sqrt, [1] reciprocal
  * (both 0 for a library whose results equal the oracle's). */
 int rt_math_selfcheck(uint64_t* mismatches);
+
+/* Debug: one scalar function of the arithmetic contract on
+ * 32-bit input patterns, evaluated by the x86 compile of the shared headers
+ * (RT_MATH_HOST: no device needed) or by a kernel on the current device
+ * (RT_MATH_DEVICE; no context, as rt_math_selfcheck).  A test holds the two
+ * sides equal over a function's whole domain (tests/test_gpu_math_fns.py).
+ *
+ * fn is an rt_math_fn; the Halton forms carry the dimension D < 24 in bits
+ * 8-12 (RT_MATH_HALTON(form, D)) and take the sample index as input.  The
+ * host has only the reference loop: host RT_MATH_HALTON_SMALL / _TAB are
+ * RT_ERR_INVALID_ARG.  _TAB exists for the dimensions the kernels keep a
+ * low-digit table for; _SMALL and _TAB refuse an index >= 3^13 = 1594323.
+ *
+ * The output is the result's 32-bit pattern; a byte (TONEMAP) or a half (F2H)
+ * is zero-extended.  Every NaN result is canonicalised, a float to 0x7FC00000
+ * and a half to 0x7E00: NaN signs and payloads differ between x86 and gfx950.
+ *
+ * Added without a change of RTPT_ABI_VERSION: detect them by the presence of
+ * the symbol rt_debug_math_values (dlsym). */
+typedef enum rt_math_fn {
+    RT_MATH_SIN = 0,          /* first output of sincos_pt(x)                          */
+    RT_MATH_COS = 1,          /* second output of sincos_pt(x)                         */
+    RT_MATH_LOG = 2,          /* log_pt(x)                                             */
+    RT_MATH_EXP = 3,          /* exp_pt(x)                                             */
+    RT_MATH_POW_GAMMA = 4,    /* pow_pt(x, 1.0f / 2.2f)                                */
+    RT_MATH_SQRT = 5,         /* sqrt_cr(x); host sqrtf(x)                             */
+    RT_MATH_RCP = 6,          /* rcp_cr(x); host 1.0f / x                              */
+    RT_MATH_F2H = 7,          /* float -> half bits: __float2half_rn; host to_half     */
+    RT_MATH_H2F = 8,          /* half bits (low 16) -> float: __half2float; from_half  */
+    RT_MATH_TONEMAP = 9,      /* tonemap_channel(half -> float): the RGBA8 epilogue
+                                 after its fp16 round trip, one channel's byte         */
+    RT_MATH_MIS_UNIT = 10,    /* mis_unit(mis_hash(x))                                 */
+    RT_MATH_HALTON_LOOP = 11, /* halton<D>(i): the reference loop, any index           */
+    RT_MATH_HALTON_SMALL = 12,/* halton_small<D>(i), device only                       */
+    RT_MATH_HALTON_TAB = 13   /* halton_tab<D>(i, LDS tables), device only             */
+} rt_math_fn;
+#define RT_MATH_HALTON(form, D) ((uint32_t)(form) | ((uint32_t)(D) << 8))
+#define RT_MATH_HOST   0u
+#define RT_MATH_DEVICE 1u
+#define RT_MATH_VALUES_MAX (1u << 24) /* most inputs of one rt_debug_math_values call */
+
+/* out_bits[j] = fn(in_bits[j]) for j < n <= RT_MATH_VALUES_MAX (host arrays). */
+int rt_debug_math_values(uint32_t fn, uint32_t where, const uint32_t* in_bits, uint64_t n, uint32_t* out_bits);
+
+/* Two checksums per chunk of 2^chunk_log2 consecutive inputs first_bits + j,
+ * j < count (first_bits + count <= 2^32; 6 <= chunk_log2 <= 31; the last chunk
+ * may be partial).  With out = fn(input) and j' the offset in chunk c:
+ *   sums[2c]     = sum of out            mod 2^64
+ *   sums[2c + 1] = sum of out * (2j'+1)  mod 2^64
+ * The second catches compensating errors and swapped outputs.  `sums` holds
+ * 2 * ceil(count / 2^chunk_log2) values.  The host side runs on host_threads
+ * (1..256) threads; the device side runs one workgroup per chunk. */
+int rt_debug_math_sums(uint32_t fn, uint32_t where, uint32_t first_bits, uint64_t count, uint32_t chunk_log2,
+                       uint32_t host_threads, uint64_t* sums);
 
 /* Hash of the sources this library was built from (gpuraytracer_amd/srchash.py:
  * csrc/ + include/): a loader can refuse a stale binary. */
