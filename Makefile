@@ -14,7 +14,7 @@ HOSTCXX ?= /opt/rocm/llvm/bin/clang++
 HIPFLAGS := $(COMMON) --offload-arch=$(ARCH) -fno-slp-vectorize $(EXTRA)
 HOSTFLAGS := $(COMMON) -D__HIP_PLATFORM_AMD__ -isystem /opt/rocm/include $(EXTRA)
 
-OBJS := $(BLD)/rt_kernel.o $(BLD)/rt_rays.o $(BLD)/rt_aov.o $(BLD)/rt_denoise.o $(BLD)/rt_mis.o $(BLD)/rt_lbvh.o $(BLD)/rt_gsah.o $(BLD)/rt_mathcheck.o $(BLD)/rt_api.o $(BLD)/rt_scene.o $(BLD)/rt_image.o
+OBJS := $(BLD)/rt_kernel.o $(BLD)/rt_rays.o $(BLD)/rt_aov.o $(BLD)/rt_denoise.o $(BLD)/rt_mis.o $(BLD)/rt_lbvh.o $(BLD)/rt_gsah.o $(BLD)/rt_refit.o $(BLD)/rt_mathcheck.o $(BLD)/rt_api.o $(BLD)/rt_scene.o $(BLD)/rt_image.o
 HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp
 
 LIB ?= $(PKG)/librtpt.so
@@ -75,7 +75,7 @@ $(ASAN)/%.o: $(SRC)/%.cpp $(HDRS) | $(ASAN)
 
 $(ASAN)/rt_image.o: $(SRC)/rt_half.h
 
-$(ASAN)/librtpt.so: $(ASAN_HOST) $(BLD)/rt_kernel.o $(BLD)/rt_rays.o $(BLD)/rt_aov.o $(BLD)/rt_denoise.o $(BLD)/rt_mis.o $(BLD)/rt_lbvh.o $(BLD)/rt_gsah.o $(BLD)/rt_mathcheck.o
+$(ASAN)/librtpt.so: $(ASAN_HOST) $(BLD)/rt_kernel.o $(BLD)/rt_rays.o $(BLD)/rt_aov.o $(BLD)/rt_denoise.o $(BLD)/rt_mis.o $(BLD)/rt_lbvh.o $(BLD)/rt_gsah.o $(BLD)/rt_refit.o $(BLD)/rt_mathcheck.o
 	$(HOSTCXX) -shared $(SAN) -o $@ $^ -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 
 $(ASAN)/liboracle.so: oracle/pt_oracle.c oracle/pt_oracle.h include/rt_types.h | $(ASAN)

@@ -142,6 +142,17 @@ class TriBvhDump(ctypes.Structure):  # rt_tri_bvh_dump
 
 assert ctypes.sizeof(TriBvhDump) == 48
 
+RT_UPDATE_REBUILD = 0x1  # rt_update_scene: rebuild the triangle BVH instead of refitting it
+
+
+class UpdateStats(ctypes.Structure):  # rt_update_stats
+    _fields_ = [("tri_bvh", ctypes.c_uint32), ("updates", ctypes.c_uint32), ("compile_ms", ctypes.c_float),
+                ("upload_ms", ctypes.c_float), ("tri_bvh_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+assert ctypes.sizeof(UpdateStats) == 32
+
 
 class TileLayout(ctypes.Structure):  # rt_tile_layout_info
     _fields_ = [("rows", ctypes.c_uint32), ("rows_max", ctypes.c_uint32),
@@ -229,6 +240,10 @@ SIGNATURES = {
     "rt_debug_tri_bvh": (ctypes.c_int, [_P, ctypes.POINTER(TriBvhDump)]),
     "rt_debug_tri_bvh_host": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(CreateOptions),
                                              ctypes.POINTER(TriBvhDump)]),
+    "rt_update_scene": (ctypes.c_int, [_P, ctypes.POINTER(SceneDesc), ctypes.c_uint32]),
+    "rt_update_info": (ctypes.c_int, [_P, ctypes.POINTER(UpdateStats)]),
+    "rt_debug_tri_bvh_refit_host": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(CreateOptions),
+                                                   ctypes.POINTER(SceneDesc), ctypes.POINTER(TriBvhDump)]),
     "rt_math_selfcheck": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rt_debug_math_values": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_uint64, _P]),
     "rt_debug_math_sums": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,

@@ -101,6 +101,16 @@ struct rt_ctx {
     rt::SceneMem scene_mem = rt::SceneMem::kAuto;  // rt_create_options.scene_layout
     uint32_t walk = 0;   // rt_create_options.walk_scheduler
     uint32_t walk_leaf_den = 0;  // rt_create_options.walk_leaf_den
+    // what a later build needs of rt_create_options (rt_update_scene)
+    uint32_t tri_leaf_opt = rt::kTriLeafMax;
+    double tri_leaf_cost = 1.0;
+    rt::BuildOptions build_opt;
+    size_t scene_bytes[12] = {};     // bytes of the record arrays on the device (upload_scene)
+    uint32_t* d_refit = nullptr;     // rt_refit.hip: parents and counters of the built tree (first refit)
+    hipEvent_t ev_u0 = nullptr, ev_u1 = nullptr;  // round the refit's kernels
+    std::string broken;              // non-empty: an update failed halfway (every render / query: RT_ERR_STATE)
+    bool updated = false;
+    rt_update_stats update{};        // the last successful rt_update_scene
     std::string err;
 };
 
@@ -193,6 +203,135 @@ void set_tables(rt::KParams* K, const rt::SceneTables& t) {
     K->pair_free = t.pair_free;
 }
 
+// The record arrays of c->scene on the device, for rt_create_ex (nothing
+// allocated yet) and rt_update_scene alike: an array is allocated again only
+// when its size changes (c->scene_bytes; an empty array is a null pointer, as
+// the kernels' arguments expect), the copies are enqueued and waited for once.
+hipError_t upload_scene(rt_ctx* c) {
+    const rt::CompiledScene& s = c->scene;
+    const struct { void** d; const void* src; size_t bytes; } arrays[12] = {
+        {(void**)&c->d_tri_isect, s.tri_isect.data(), s.tri_isect.size() * sizeof(rt::TriIsect)},
+        {(void**)&c->d_tri_shade, s.tri_shade.data(), s.tri_shade.size() * sizeof(rt::TriShade)},
+        {(void**)&c->d_pair_isect, s.pair_isect.data(), s.pair_isect.size() * sizeof(rt::PairIsect)},
+        {(void**)&c->d_clusters, s.clusters.data(), s.clusters.size() * sizeof(float)},
+        {(void**)&c->d_sph_lds, s.sph_lds.data(), s.sph_lds.size() * sizeof(uint32_t)},
+        {(void**)&c->d_sph_lds_id, s.sph_lds_id.data(), s.sph_lds_id.size() * sizeof(uint16_t)},
+        {(void**)&c->d_sph_box, s.sph_box.data(), s.sph_box.size() * sizeof(uint32_t)},
+        {(void**)&c->d_sph_isect, s.sph_isect.data(), s.sph_isect.size() * sizeof(rt::SphIsect)},
+        {(void**)&c->d_sph_shade, s.sph_shade.data(), s.sph_shade.size() * sizeof(rt::SphShade)},
+        {(void**)&c->d_sph_nodes, s.sph_nodes.data(), s.sph_nodes.size() * sizeof(rt::BvhNode)},
+        {(void**)&c->d_sph_perm, s.sph_perm.data(), s.sph_perm.size() * sizeof(uint32_t)},
+        {(void**)&c->d_mis_shade, s.mis_shade.data(), s.mis_shade.size() * sizeof(rt::MisShade)}};
+    hipError_t e;
+    for (int k = 0; k < 12; ++k) {
+        const auto& a = arrays[k];
+        if (c->scene_bytes[k] != a.bytes) {
+            (void)hipFree(*a.d);
+            *a.d = nullptr;
+            c->scene_bytes[k] = 0;
+            if (a.bytes && (e = hipMalloc(a.d, a.bytes)) != hipSuccess) return e;
+            c->scene_bytes[k] = a.bytes;
+        }
+        if (a.bytes && (e = hipMemcpyAsync(*a.d, a.src, a.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+            return e;
+    }
+    return hipStreamSynchronize(c->stream);
+}
+
+// rt_create's rule: a triangle BVH above kTriBvhMinTriangles or when the
+// records do not fit the LDS layouts, or when the layout is forced.
+bool needs_tri_bvh(const rt_ctx* c) {
+    const rt::CompiledScene& s = c->scene;
+    const uint32_t nT = (uint32_t)s.tri_isect.size();
+    const size_t lds_pairs = rt::kernel_lds_bytes(nT, (uint32_t)s.pair_isect.size(), 0, 0);
+    const size_t lds_single = rt::kernel_lds_bytes(nT, 0, 0, 0);
+    return nT > 0 && (c->scene_mem == rt::SceneMem::kTriBvh ||
+                      (c->scene_mem == rt::SceneMem::kAuto &&
+                       (nT > rt::kTriBvhMinTriangles || std::min(lds_pairs, lds_single) > rt::kMaxLdsBytes)));
+}
+
+void free_tri_bvh(rt_ctx* c) {
+    (void)hipFree(c->d_tri_nodes);
+    (void)hipFree(c->d_tri_sorted);
+    (void)hipFree(c->d_tri_perm);
+    (void)hipFree(c->d_refit);  // the parents of the tree that goes
+    c->d_tri_nodes = nullptr;
+    c->d_tri_sorted = nullptr;
+    c->d_tri_perm = nullptr;
+    c->d_refit = nullptr;
+    c->tri_bvh_nodes = 0;
+    c->tri_bvh_build_used = 0;
+    c->tri_bvh_temp_bytes = 0;
+}
+
+// The triangle BVH of c->scene from the uploaded d_tri_isect, with the
+// context's builder and options (replaces setupAccelerationStructures,
+// computeShader.swift:45-97); a tree the context holds is freed first.
+int build_tri_bvh(rt_ctx* c, std::string* msg) {
+    using clk = std::chrono::steady_clock;
+    free_tri_bvh(c);
+    const rt::CompiledScene& s = c->scene;
+    const uint32_t nT = (uint32_t)s.tri_isect.size();
+    const size_t nn = 2 * (size_t)nT - 1;
+    const auto t_build = clk::now();
+    hipError_t e;
+    if (c->tri_build == RT_TRI_BVH_GPU_SAH || c->tri_build == RT_TRI_BVH_GPU_LBVH) {
+        if ((e = hipMalloc((void**)&c->d_tri_nodes, rt::kTriCompactLayouts * nn * sizeof(uint4))) != hipSuccess ||
+            (e = hipMalloc((void**)&c->d_tri_sorted, 3 * (size_t)nT * sizeof(float4))) != hipSuccess ||
+            (e = hipMalloc((void**)&c->d_tri_perm, (size_t)nT * sizeof(uint32_t))) != hipSuccess) {
+            *msg = std::string("hipMalloc(triangle BVH): ") + hipGetErrorString(e);
+            return RT_ERR_OUT_OF_MEMORY;
+        }
+    }
+    if (c->tri_build == RT_TRI_BVH_GPU_SAH) {  // GPU binned SAH (rt_gsah.hip)
+        uint32_t total = 0;
+        size_t temp = 0;
+        if ((e = rt::build_tri_gsah(c->d_tri_isect, nT, s.margin, c->tri_leaf_opt, c->tri_leaf_cost, c->d_tri_nodes,
+                                    c->d_tri_sorted, c->d_tri_perm, &total, &temp, c->stream)) != hipSuccess) {
+            *msg = std::string("triangle BVH build: ") + hipGetErrorString(e);
+            return (e == hipErrorInvalidValue) ? RT_ERR_INVALID_ARG
+                   : (e == hipErrorOutOfMemory) ? RT_ERR_OUT_OF_MEMORY : RT_ERR_LAUNCH;
+        }
+        c->tri_bvh_nodes = total;
+        c->tri_bvh_temp_bytes = temp;
+    } else if (c->tri_build == RT_TRI_BVH_GPU_LBVH) {  // GPU Morton build (rt_lbvh.hip)
+        if ((e = rt::build_tri_lbvh(c->d_tri_isect, nT, s.tri_lo, s.tri_hi, s.margin, c->d_tri_nodes,
+                                    c->d_tri_sorted, c->d_tri_perm, c->stream)) != hipSuccess) {
+            *msg = std::string("triangle BVH build: ") + hipGetErrorString(e);
+            return (e == hipErrorInvalidValue) ? RT_ERR_INVALID_ARG : RT_ERR_LAUNCH;
+        }
+        c->tri_bvh_nodes = (uint32_t)nn;
+    } else {  // host binned SAH (rt_scene.cpp build_tri_sah), uploaded
+        std::vector<uint32_t> nodes, perm;
+        std::vector<rt::TriIsect> sorted;
+        if (!rt::build_tri_sah(s.tri_isect, s.margin, &nodes, &sorted, &perm, c->tri_leaf_opt, c->tri_leaf_cost)) {
+            *msg = "triangle BVH build: too many triangles (2^24)";
+            return RT_ERR_INVALID_ARG;
+        }
+        if ((e = upload(&c->d_tri_nodes, nodes.data(), nodes.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
+            (e = upload(&c->d_tri_sorted, sorted.data(), sorted.size() * sizeof(rt::TriIsect), c->stream)) != hipSuccess ||
+            (e = upload(&c->d_tri_perm, perm.data(), perm.size() * sizeof(uint32_t), c->stream)) != hipSuccess) {
+            *msg = std::string("triangle BVH upload: ") + hipGetErrorString(e);
+            return RT_ERR_OUT_OF_MEMORY;
+        }
+        c->tri_bvh_nodes = (uint32_t)(nodes.size() / (4 * rt::kTriCompactLayouts));
+    }
+    // the LBVH leaves hold one triangle; the SAH builds clamp the option to 1..128
+    c->tri_leaf_max = c->tri_build == RT_TRI_BVH_GPU_LBVH ? 1u : std::min(128u, std::max(1u, c->tri_leaf_opt));
+    c->tri_bvh_build_used = c->tri_build;
+    c->tri_bvh_build_ms = std::chrono::duration<float, std::milli>(clk::now() - t_build).count();
+    return RT_OK;
+}
+
+// The tail of rt_create_ex and of rt_update_scene: everything a launch takes
+// from the context that is derived from the compiled scene and its device
+// arrays.  (The ray domain is rt::ray_domain(c->scene.extent) at every query.)
+void finish_scene(rt_ctx* c) {
+    c->sph_compact = rt::sphere_compact_usable(c->scene);
+    c->tab = scene_tables(c->scene, c->tri_bvh_nodes, c);
+    c->light_mask = rt::light_mask(c->scene);
+}
+
 void release(rt_ctx* c) {
     if (!c) return;
     DeviceGuard g(c->device);
@@ -211,6 +350,7 @@ void release(rt_ctx* c) {
     (void)hipFree(c->d_tri_nodes);
     (void)hipFree(c->d_tri_sorted);
     (void)hipFree(c->d_tri_perm);
+    (void)hipFree(c->d_refit);
     (void)hipFree(c->d_mis_shade);
     (void)hipFree(c->d_mis_tab);
     (void)hipFree(c->d_out8);
@@ -226,6 +366,8 @@ void release(rt_ctx* c) {
     (void)hipFree(c->d_tile);
     (void)hipFree(c->d_gather);
     if (c->ev_tiles) (void)hipEventDestroy(c->ev_tiles);
+    if (c->ev_u0) (void)hipEventDestroy(c->ev_u0);
+    if (c->ev_u1) (void)hipEventDestroy(c->ev_u1);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -246,6 +388,7 @@ bool resolve_rows(const rt_ctx* c, const rt_render_params* p, uint32_t* start, u
 int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_device,
                 hipStream_t stream, bool sync) {
     if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is null");
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
     if (p->bounces > RT_MAX_BOUNCES)
         return fail(c, RT_ERR_INVALID_ARG,
                     "bounces > 4: Halton dimensions would leave primes[24] (sampling.metal:97)");
@@ -547,6 +690,7 @@ int ensure_staging(rt_ctx* c, void** buf, size_t* cap, size_t bytes, const char*
 
 int render_mis_impl(rt_ctx* c, const rt_mis_params* p, float* out, uint8_t* out8) {
     if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is null");
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
     if (!out && !out8) return fail(c, RT_ERR_INVALID_ARG, "both outputs are null");
     if (!c->scene.sph_isect.empty())
         return fail(c, RT_ERR_INVALID_ARG,
@@ -648,6 +792,7 @@ int render_mis_impl(rt_ctx* c, const rt_mis_params* p, float* out, uint8_t* out8
 int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, rt_ray_hit* hits, bool dev,
                     hipStream_t stream, bool sync) {
     static_assert(sizeof(rt_ray) == 32 && sizeof(rt_ray_hit) == 8, "rt_ray / rt_ray_hit layout");
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
     if (flags & ~(uint32_t)(RT_OUT_DEVICE | RT_RAYS_ANY | RT_RAYS_EXACT))
         return fail(c, RT_ERR_INVALID_ARG, "rt_trace_rays: unknown flag bits");
     if (n > 0x80000000ull) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_rays: n > 2^31");
@@ -695,6 +840,7 @@ int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, r
 int render_aov_impl(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b, bool dev, hipStream_t stream,
                     bool sync) {
     static_assert(sizeof(rt_aov_params) == 24 && sizeof(rt_aov_buffers) == 24, "rt_aov_params / rt_aov_buffers layout");
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
     if (!p) return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: params is null");
     if (!b) return fail(c, RT_ERR_INVALID_ARG, "rt_render_aov: buffers is null");
     if (!b->albedo && !b->normal_depth && !b->first_hit)
@@ -951,6 +1097,9 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
     c->scene_mem = ro.mem;
     c->walk = ro.walk;
     c->walk_leaf_den = ro.walk_leaf_den;
+    c->tri_leaf_opt = ro.tri_leaf_max;
+    c->tri_leaf_cost = ro.tri_leaf_cost;
+    c->build_opt = ro.build;
     DeviceGuard g(c->device);
     const char* err = nullptr;
     using clk = std::chrono::steady_clock;
@@ -972,81 +1121,10 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
             status = RT_ERR_NO_DEVICE; msg = std::string("hipEventCreate: ") + hipGetErrorString(e); break;
         }
         const rt::CompiledScene& s = c->scene;
-        if ((e = upload(&c->d_tri_isect, s.tri_isect.data(), s.tri_isect.size() * sizeof(rt::TriIsect), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_tri_shade, s.tri_shade.data(), s.tri_shade.size() * sizeof(rt::TriShade), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_pair_isect, s.pair_isect.data(), s.pair_isect.size() * sizeof(rt::PairIsect), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_clusters, s.clusters.data(), s.clusters.size() * sizeof(float), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_lds, s.sph_lds.data(), s.sph_lds.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_lds_id, s.sph_lds_id.data(), s.sph_lds_id.size() * sizeof(uint16_t), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_box, s.sph_box.data(), s.sph_box.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_isect, s.sph_isect.data(), s.sph_isect.size() * sizeof(rt::SphIsect), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_shade, s.sph_shade.data(), s.sph_shade.size() * sizeof(rt::SphShade), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_nodes, s.sph_nodes.data(), s.sph_nodes.size() * sizeof(rt::BvhNode), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_sph_perm, s.sph_perm.data(), s.sph_perm.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
-            (e = upload(&c->d_mis_shade, s.mis_shade.data(), s.mis_shade.size() * sizeof(rt::MisShade), c->stream)) != hipSuccess) {
+        if ((e = upload_scene(c)) != hipSuccess) {
             status = RT_ERR_OUT_OF_MEMORY; msg = std::string("scene upload: ") + hipGetErrorString(e); break;
         }
-        // Triangle BVH, built on the device (replaces setupAccelerationStructures,
-        // computeShader.swift:45-97): above kTriBvhMinTriangles or when the records
-        // do not fit the LDS layouts, or when forced (RTPT_SCENE_MEM=bvh).
-        const uint32_t nT = (uint32_t)s.tri_isect.size();
-        const size_t lds_pairs = rt::kernel_lds_bytes(nT, (uint32_t)s.pair_isect.size(), 0, 0);
-        const size_t lds_single = rt::kernel_lds_bytes(nT, 0, 0, 0);
-        const bool need_bvh = nT > 0 && (c->scene_mem == rt::SceneMem::kTriBvh ||
-                                         (c->scene_mem == rt::SceneMem::kAuto &&
-                                          (nT > rt::kTriBvhMinTriangles ||
-                                           std::min(lds_pairs, lds_single) > rt::kMaxLdsBytes)));
-        if (need_bvh) {
-            const size_t nn = 2 * (size_t)nT - 1;
-            const auto t_build = clk::now();
-            if (c->tri_build == RT_TRI_BVH_GPU_SAH) {  // GPU binned SAH (rt_gsah.hip)
-                if ((e = hipMalloc((void**)&c->d_tri_nodes, rt::kTriCompactLayouts * nn * sizeof(uint4))) != hipSuccess ||
-                    (e = hipMalloc((void**)&c->d_tri_sorted, 3 * (size_t)nT * sizeof(float4))) != hipSuccess ||
-                    (e = hipMalloc((void**)&c->d_tri_perm, (size_t)nT * sizeof(uint32_t))) != hipSuccess) {
-                    status = RT_ERR_OUT_OF_MEMORY; msg = std::string("hipMalloc(triangle BVH): ") + hipGetErrorString(e); break;
-                }
-                uint32_t total = 0;
-                size_t temp = 0;
-                if ((e = rt::build_tri_gsah(c->d_tri_isect, nT, s.margin, ro.tri_leaf_max, ro.tri_leaf_cost,
-                                            c->d_tri_nodes, c->d_tri_sorted, c->d_tri_perm, &total, &temp,
-                                            c->stream)) != hipSuccess) {
-                    status = (e == hipErrorInvalidValue) ? RT_ERR_INVALID_ARG
-                             : (e == hipErrorOutOfMemory) ? RT_ERR_OUT_OF_MEMORY : RT_ERR_LAUNCH;
-                    msg = std::string("triangle BVH build: ") + hipGetErrorString(e); break;
-                }
-                c->tri_bvh_nodes = total;
-                c->tri_bvh_temp_bytes = temp;
-            } else if (c->tri_build == RT_TRI_BVH_GPU_LBVH) {  // GPU Morton build (rt_lbvh.hip)
-                if ((e = hipMalloc((void**)&c->d_tri_nodes, rt::kTriCompactLayouts * nn * sizeof(uint4))) != hipSuccess ||
-                    (e = hipMalloc((void**)&c->d_tri_sorted, 3 * (size_t)nT * sizeof(float4))) != hipSuccess ||
-                    (e = hipMalloc((void**)&c->d_tri_perm, (size_t)nT * sizeof(uint32_t))) != hipSuccess) {
-                    status = RT_ERR_OUT_OF_MEMORY; msg = std::string("hipMalloc(triangle BVH): ") + hipGetErrorString(e); break;
-                }
-                if ((e = rt::build_tri_lbvh(c->d_tri_isect, nT, s.tri_lo, s.tri_hi, s.margin, c->d_tri_nodes,
-                                            c->d_tri_sorted, c->d_tri_perm, c->stream)) != hipSuccess) {
-                    status = (e == hipErrorInvalidValue) ? RT_ERR_INVALID_ARG : RT_ERR_LAUNCH;
-                    msg = std::string("triangle BVH build: ") + hipGetErrorString(e); break;
-                }
-            } else {  // host binned SAH (rt_scene.cpp build_tri_sah), uploaded
-                std::vector<uint32_t> nodes, perm;
-                std::vector<rt::TriIsect> sorted;
-                if (!rt::build_tri_sah(s.tri_isect, s.margin, &nodes, &sorted, &perm, ro.tri_leaf_max,
-                                       ro.tri_leaf_cost)) {
-                    status = RT_ERR_INVALID_ARG; msg = "triangle BVH build: too many triangles (2^24)"; break;
-                }
-                if ((e = upload(&c->d_tri_nodes, nodes.data(), nodes.size() * sizeof(uint32_t), c->stream)) != hipSuccess ||
-                    (e = upload(&c->d_tri_sorted, sorted.data(), sorted.size() * sizeof(rt::TriIsect), c->stream)) != hipSuccess ||
-                    (e = upload(&c->d_tri_perm, perm.data(), perm.size() * sizeof(uint32_t), c->stream)) != hipSuccess) {
-                    status = RT_ERR_OUT_OF_MEMORY; msg = std::string("triangle BVH upload: ") + hipGetErrorString(e); break;
-                }
-                c->tri_bvh_nodes = (uint32_t)(nodes.size() / (4 * rt::kTriCompactLayouts));
-            }
-            if (c->tri_build == RT_TRI_BVH_GPU_LBVH) c->tri_bvh_nodes = (uint32_t)nn;
-            // the LBVH leaves hold one triangle; the SAH builds clamp the option to 1..128
-            c->tri_leaf_max = c->tri_build == RT_TRI_BVH_GPU_LBVH ? 1u : std::min(128u, std::max(1u, ro.tri_leaf_max));
-            c->tri_bvh_build_used = c->tri_build;
-            c->tri_bvh_build_ms = std::chrono::duration<float, std::milli>(clk::now() - t_build).count();
-        }
+        if (needs_tri_bvh(c) && (status = build_tri_bvh(c, &msg)) != RT_OK) break;
         const size_t npx = (size_t)s.cam.W * (size_t)s.cam.H;
         if ((e = hipMalloc((void**)&c->d_seeds, npx * sizeof(uint32_t))) != hipSuccess) {
             status = RT_ERR_OUT_OF_MEMORY; msg = std::string("hipMalloc(seeds): ") + hipGetErrorString(e); break;
@@ -1057,10 +1135,136 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
         delete c;
         return fail(nullptr, status, msg);
     }
-    c->sph_compact = rt::sphere_compact_usable(c->scene);
-    c->tab = scene_tables(c->scene, c->tri_bvh_nodes, c);
-    c->light_mask = rt::light_mask(c->scene);
+    finish_scene(c);
     *out_ctx = c;
+    return RT_OK;
+}
+
+int rt_update_scene(rt_ctx* c, const rt_scene_desc* d, uint32_t flags) {
+    static_assert(sizeof(rt_update_stats) == 32, "rt_update_stats layout");
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    if (!d) return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: scene is null");
+    if (!d->camera) return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: camera is null");
+    if (!d->square_lights || d->n_square_lights < 1)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: square_lights[0] is required");
+    if (flags & ~(uint32_t)RT_UPDATE_REBUILD) return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: unknown bits in flags");
+    if (d->n_triangles != c->scene.tri_isect.size())
+        return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: n_triangles differs from the context's (" +
+                                               std::to_string(c->scene.tri_isect.size()) + ")");
+    if (d->n_spheres != c->scene.sph_shade.size())
+        return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: n_spheres differs from the context's (" +
+                                               std::to_string(c->scene.sph_shade.size()) + ")");
+    if (d->camera->resolution.x != c->scene.cam.W || d->camera->resolution.y != c->scene.cam.H)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: camera resolution differs from the context's");
+    if (d->device != c->device) return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: device differs from the context's");
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
+    const auto t_all = clk::now();
+    rt::CompiledScene next;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0], d->spheres,
+                           d->n_spheres, &next, &err, c->build_opt))
+        return fail(c, RT_ERR_INVALID_ARG, std::string("rt_update_scene: ") + err);
+    if (next.tri_isect.size() != c->scene.tri_isect.size() || next.sph_shade.size() != c->scene.sph_shade.size())
+        return fail(c, RT_ERR_INVALID_ARG, "rt_update_scene: the compiled scene changed its primitive counts");
+    rt_update_stats st{};
+    st.compile_ms = ms_since(t_all);
+
+    // From here on the device arrays change: a failure leaves the context marked.
+    DeviceGuard g(c->device);
+    auto broken = [&](int status, const std::string& what) {
+        c->broken = "the context holds a half-updated scene (" + what + "): rt_update_scene must succeed first";
+        return fail(c, status, "rt_update_scene: " + what);
+    };
+    hipError_t e;
+    if (c->tiles_pending) (void)hipEventSynchronize(c->ev_tiles);
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return broken(RT_ERR_LAUNCH, std::string("stream: ") + hipGetErrorString(e));
+    if (!c->ev_u0 && ((e = hipEventCreate(&c->ev_u0)) != hipSuccess || (e = hipEventCreate(&c->ev_u1)) != hipSuccess))
+        return broken(RT_ERR_OUT_OF_MEMORY, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    c->broken = "rt_update_scene in progress";
+    c->sum_valid = false;
+    c->scene = std::move(next);
+    const auto t_up = clk::now();
+    if ((e = upload_scene(c)) != hipSuccess) return broken(RT_ERR_OUT_OF_MEMORY, std::string("scene upload: ") + hipGetErrorString(e));
+    st.upload_ms = ms_since(t_up);
+
+    const bool need = needs_tri_bvh(c), have = c->tri_bvh_build_used && c->d_tri_nodes;
+    const auto t_bvh = clk::now();
+    if (need && have && !(flags & RT_UPDATE_REBUILD)) {  // refit (rt_refit.hip)
+        bool table_made = false;
+        e = rt::refit_tri_bvh(c->d_tri_isect, (uint32_t)c->scene.tri_isect.size(), c->scene.margin, c->d_tri_nodes,
+                              c->tri_bvh_nodes, c->d_tri_sorted, c->d_tri_perm, &c->d_refit, &table_made, c->ev_u0,
+                              c->ev_u1, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the one wait of the update's device work
+        if (e != hipSuccess)
+            return broken(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_LAUNCH,
+                          std::string("triangle BVH refit: ") + hipGetErrorString(e));
+        uint32_t bad = 0;
+        if (table_made && ((e = rt::refit_format_errors(c->d_refit, c->tri_bvh_nodes, &bad)) != hipSuccess || bad))
+            return broken(RT_ERR_LAUNCH, "triangle BVH refit: the tree is outside the format of its builders");
+        if ((e = hipEventElapsedTime(&st.tri_bvh_ms, c->ev_u0, c->ev_u1)) != hipSuccess)
+            return broken(RT_ERR_LAUNCH, std::string("hipEventElapsedTime: ") + hipGetErrorString(e));
+        st.tri_bvh = 1;
+    } else if (need) {  // as rt_create: the context's builder
+        std::string msg;
+        const int status = build_tri_bvh(c, &msg);
+        if (status != RT_OK) return broken(status == RT_ERR_INVALID_ARG ? RT_ERR_LAUNCH : status, msg);
+        st.tri_bvh_ms = ms_since(t_bvh);
+        st.tri_bvh = 2;
+        c->scene_compile_ms = st.compile_ms;
+    } else {
+        free_tri_bvh(c);
+    }
+    finish_scene(c);
+    c->broken.clear();
+    st.updates = c->update.updates + 1;
+    st.total_ms = ms_since(t_all);
+    c->update = st;
+    c->updated = true;
+    return RT_OK;
+}
+
+int rt_update_info(const rt_ctx* c, rt_update_stats* info) {
+    if (!c || !info) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (!c->updated)
+        return fail(const_cast<rt_ctx*>(c), RT_ERR_STATE, "rt_update_info: no successful rt_update_scene on this context yet");
+    *info = c->update;
+    return RT_OK;
+}
+
+int rt_debug_tri_bvh_refit_host(const rt_scene_desc* from, const rt_create_options* opt, const rt_scene_desc* to,
+                                rt_tri_bvh_dump* dump) {
+    if (!from || !to || !dump || !from->camera || !from->square_lights || !to->camera || !to->square_lights)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (from->n_triangles != to->n_triangles)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "rt_debug_tri_bvh_refit_host: n_triangles of the two scenes differ");
+    Resolved ro;
+    const char* why = nullptr;
+    if (!resolve_options(opt, &ro, &why)) return fail(nullptr, RT_ERR_INVALID_ARG, why);
+    rt::CompiledScene a, b;
+    const char* err = nullptr;
+    if (!rt::compile_scene(*from->camera, from->materials, from->vertices, from->n_triangles, from->square_lights[0],
+                           from->spheres, from->n_spheres, &a, &err, ro.build) ||
+        !rt::compile_scene(*to->camera, to->materials, to->vertices, to->n_triangles, to->square_lights[0],
+                           to->spheres, to->n_spheres, &b, &err, ro.build))
+        return fail(nullptr, RT_ERR_INVALID_ARG, err);
+    const size_t nT = a.tri_isect.size();
+    if (nT == 0) return fail(nullptr, RT_ERR_INVALID_ARG, "the scene has no triangles");
+    if (b.tri_isect.size() != nT) return fail(nullptr, RT_ERR_INVALID_ARG, "n_triangles of the compiled scenes differ");
+    std::vector<uint32_t> nodes, perm;
+    std::vector<rt::TriIsect> sorted;
+    if (!rt::build_tri_sah(a.tri_isect, a.margin, &nodes, &sorted, &perm, ro.tri_leaf_max, ro.tri_leaf_cost))
+        return fail(nullptr, RT_ERR_INVALID_ARG, "triangle BVH build: too many triangles (2^24)");
+    if (!rt::refit_tri_bvh_host(b.tri_isect, b.margin, &nodes, perm, &sorted))
+        return fail(nullptr, RT_ERR_STATE, "triangle BVH refit: the tree is outside the format");
+    dump->n_triangles = (uint32_t)nT;
+    dump->nodes_per_layout = (uint32_t)(nodes.size() / (4 * rt::kTriCompactLayouts));
+    dump->leaf_max = std::min(128u, std::max(1u, ro.tri_leaf_max));
+    dump->margin = b.margin;
+    if (dump->nodes) memcpy(dump->nodes, nodes.data(), nodes.size() * sizeof(uint32_t));
+    if (dump->sorted) memcpy(dump->sorted, sorted.data(), nT * sizeof(rt::TriIsect));
+    if (dump->perm) memcpy(dump->perm, perm.data(), nT * sizeof(uint32_t));
+    if (dump->isect) memcpy(dump->isect, b.tri_isect.data(), nT * sizeof(rt::TriIsect));
     return RT_OK;
 }
 
@@ -1434,6 +1638,7 @@ int rt_build_info(const rt_ctx* c, rt_build_stats* info) {
 
 int rt_debug_tri_bvh(const rt_ctx* c, rt_tri_bvh_dump* dump) {
     if (!c || !dump) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (!c->broken.empty()) return fail(const_cast<rt_ctx*>(c), RT_ERR_STATE, c->broken);
     if (!c->tri_bvh_build_used || !c->d_tri_nodes) return RT_ERR_STATE;
     const size_t nT = c->scene.tri_isect.size(), nn = c->tri_bvh_nodes;
     dump->n_triangles = (uint32_t)nT;

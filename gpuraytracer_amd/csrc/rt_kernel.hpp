@@ -356,6 +356,21 @@ hipError_t build_tri_gsah(const float4* d_tri, uint32_t n, float margin, uint32_
 // ceil(n / 1024) words.
 hipError_t scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tile_sums, hipStream_t s);
 
+// Refit of a built triangle BVH onto new id-order records (rt_refit.hip,
+// DESIGN.md §3.25): d_sorted[k] = d_tri[d_perm[k]] and new fp16 boxes in every
+// entry of the 8 layouts of `total` entries; the fourth word of every entry
+// and d_perm are only read.  *d_table: the per-tree table of parents and
+// arrival counters (tri_refit_table_bytes), allocated and filled when null
+// (*table_made; the caller frees it with the tree, and reads
+// refit_format_errors once the stream is idle: entries outside the format, 0
+// for any builder's tree).  ev0 / ev1 are recorded round the refit's own
+// memset and kernels.  Enqueues only: no synchronisation.
+size_t tri_refit_table_bytes(uint32_t total);
+hipError_t refit_tri_bvh(const float4* d_tri, uint32_t n, float margin, uint4* d_nodes, uint32_t total,
+                         float4* d_sorted, const uint32_t* d_perm, uint32_t** d_table, bool* table_made,
+                         hipEvent_t ev0, hipEvent_t ev1, hipStream_t s);
+hipError_t refit_format_errors(const uint32_t* d_table, uint32_t total, uint32_t* bad);
+
 hipError_t launch_fill_seeds(uint32_t* seeds, uint64_t key, uint64_t n, hipStream_t stream);
 // The shipped short sqrt / reciprocal (rt_math.h sqrt_cr, rcp_cr) against IEEE
 // sqrtf and 1/x over every float on the current device: mismatch counts.

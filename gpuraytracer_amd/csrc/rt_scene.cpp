@@ -790,6 +790,71 @@ bool build_tri_sah(const std::vector<TriIsect>& tri, float margin, std::vector<u
     return true;
 }
 
+// The refit of rt_refit.hip on the host, layout by layout: children follow
+// their parent in a preorder layout, so one pass from the last entry to the
+// first meets every child before its parent.  A leaf plane = fp32 min / max
+// over its triangles' v0, v0 + e1, v0 + e2, padded by the margin in fp32 and
+// rounded outward; an inner plane = min / max of its children's fp16 planes
+// (of -0 and +0 the min is -0, the max +0, as on the device).
+bool refit_tri_bvh_host(const std::vector<TriIsect>& tri, float margin, std::vector<uint32_t>* nodes,
+                        const std::vector<uint32_t>& perm, std::vector<TriIsect>* sorted) {
+    const size_t n = tri.size();
+    if (n == 0 || perm.size() != n || nodes->empty() || nodes->size() % 32) return false;
+    const size_t total = nodes->size() / 32;
+    sorted->resize(n);
+    for (size_t k = 0; k < n; ++k) {
+        if (perm[k] >= n) return false;
+        (*sorted)[k] = tri[perm[k]];
+    }
+    auto value = [](uint32_t bits) {
+        const uint16_t b = (uint16_t)bits;
+        _Float16 h;
+        memcpy(&h, &b, 2);
+        return (float)h;
+    };
+    for (uint32_t oct = 0; oct < 8; ++oct) {
+        uint32_t* L = nodes->data() + (size_t)oct * total * 4;
+        for (size_t i = total; i-- > 0;) {
+            uint32_t* w = L + 4 * i;
+            uint32_t h[6];
+            if (!(w[3] & 0x80000000u)) {
+                const size_t first = w[3] & 0xFFFFFFu, count = (w[3] >> 24) + 1u;
+                if (first + count > n) return false;
+                float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+                for (size_t k = first; k < first + count; ++k) {
+                    const float* q = (*sorted)[k].q;
+                    for (int a = 0; a < 3; ++a) {
+                        const float v0 = q[a], v1 = q[a] + q[3 + a], v2 = q[a] + q[6 + a];
+                        lo[a] = fminf(lo[a], fminf(v0, fminf(v1, v2)));
+                        hi[a] = fmaxf(hi[a], fmaxf(v0, fmaxf(v1, v2)));
+                    }
+                }
+                for (int a = 0; a < 3; ++a) {
+                    h[a] = half_dir(lo[a] - margin, -1);
+                    h[3 + a] = half_dir(hi[a] + margin, +1);
+                    if ((oct >> a) & 1u) std::swap(h[a], h[3 + a]);
+                }
+            } else {
+                if (i + 2 >= total) return false;
+                const uint32_t w1 = L[4 * (i + 1) + 3];
+                const size_t c2 = (w1 & 0x80000000u) ? (size_t)(w1 & 0x7FFFFFFFu) - (size_t)oct * total : i + 2;
+                if (c2 <= i + 1 || c2 >= total) return false;
+                const uint32_t *A = L + 4 * (i + 1), *B = L + 4 * c2;
+                for (int s = 0; s < 6; ++s) {
+                    const uint32_t x = (A[s / 2] >> (16 * (s % 2))) & 0xFFFFu, y = (B[s / 2] >> (16 * (s % 2))) & 0xFFFFu;
+                    const float fx = value(x), fy = value(y);
+                    const bool is_hi = (s >= 3) != (((oct >> (s % 3)) & 1u) != 0);
+                    h[s] = is_hi ? (fx > fy ? x : (fy > fx ? y : (x & y))) : (fx < fy ? x : (fy < fx ? y : (x | y)));
+                }
+            }
+            w[0] = h[0] | h[1] << 16;
+            w[1] = h[2] | h[3] << 16;
+            w[2] = h[4] | h[5] << 16;
+        }
+    }
+    return true;
+}
+
 // Pair layout: triangles (2k, 2k+1) with the same v0 and one common edge
 // vector S (bitwise, as computed above).  All-or-nothing, so the kernel keeps
 // testing primitives in id order.

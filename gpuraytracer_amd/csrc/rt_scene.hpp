@@ -155,6 +155,13 @@ bool build_tri_sah(const std::vector<TriIsect>& tri, float margin, std::vector<u
                    std::vector<TriIsect>* sorted, std::vector<uint32_t>* perm,
                    uint32_t leaf_max = kTriLeafMax, double trav_cost = 1.0);
 
+// Host restatement of the device refit (rt_refit.hip): the
+// topology of `nodes` (8 layouts of nodes->size() / 32 entries) and `perm` are
+// kept, *sorted = tri in leaf order and every box is made again from them with
+// the builders' rule.  False when a word is outside the format.
+bool refit_tri_bvh_host(const std::vector<TriIsect>& tri, float margin, std::vector<uint32_t>* nodes,
+                        const std::vector<uint32_t>& perm, std::vector<TriIsect>* sorted);
+
 // Speed-only choices of the host builds (rt_create_options, include/rtpt.h):
 // none of them changes a rendered value.
 struct BuildOptions {

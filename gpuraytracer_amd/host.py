@@ -19,10 +19,10 @@ from dataclasses import dataclass, fields
 import numpy as np
 
 from ._native import (MATH_FNS, RT_MATH_DEVICE, RT_MATH_HOST, RT_MATH_VALUES_MAX, LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
-                      RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, TRI_BUILDS, WALKS,
+                      RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, RT_UPDATE_REBUILD, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
                       RenderParamsC,
-                      RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, float3,
+                      RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, UpdateStats, float3,
                       lib)
 
 DEFAULT_SEED_KEY = 0x5EED00000000
@@ -362,6 +362,18 @@ class Scene:
         return _tri_bvh_dump(lambda d: _check(lib.rt_debug_tri_bvh_host(ctypes.byref(desc), opt, ctypes.byref(d))),
                              n, max(2 * n - 1, 1))
 
+    def tri_bvh_refit_host(self, updated: "Scene", options: "Options | None" = None) -> dict:
+        """``tri_bvh_host(options)`` of this scene refitted onto the triangles
+        of ``updated`` (rt_debug_tri_bvh_refit_host; no device): what a
+        ``tri_build="host"`` context created from this scene holds after
+        ``Renderer.update_scene(updated)``.  Same dict as ``tri_bvh_host``."""
+        n = self.n_triangles
+        opt = None if options is None else ctypes.byref(options.c())
+        a, b = self.desc(), updated.desc()
+        return _tri_bvh_dump(lambda d: _check(lib.rt_debug_tri_bvh_refit_host(ctypes.byref(a), opt, ctypes.byref(b),
+                                                                              ctypes.byref(d))),
+                             n, max(2 * n - 1, 1))
+
     def ray_domain(self) -> dict:
         """The exactness domain of ``Renderer.trace_rays`` for this scene
         (rt_debug_ray_domain): ``origin_max``,
@@ -474,6 +486,28 @@ class Renderer:
 
     def __exit__(self, *exc):
         self.close()
+
+    def update_scene(self, scene: Scene, rebuild: bool = False):
+        """rt_update_scene: replace the context's scene in place (same triangle
+        and sphere counts and resolution).  Afterwards every call returns what
+        a new ``Renderer(scene, options=...)`` with the same seeds returns, bit
+        for bit.  The triangle BVH is refitted on the device (its topology
+        kept), or rebuilt by the context's builder with ``rebuild``.  Seeds are
+        kept, the running sum of ``keep_sum`` is dropped.  An argument error
+        (RtError, RT_ERR_INVALID_ARG) leaves the context as it was."""
+        _check(lib.rt_update_scene(self._ctx, ctypes.byref(scene.desc(self.device)),
+                                   RT_UPDATE_REBUILD if rebuild else 0), self._ctx)
+        self.scene = scene
+
+    def update_info(self) -> dict:
+        """rt_update_info of the last successful ``update_scene``: ``tri_bvh``
+        (0 no tree, 1 refitted, 2 rebuilt), ``updates`` so far, and the wall ms
+        of the compile, the upload and the whole call; ``tri_bvh_ms`` is the
+        refit kernels' device time or the rebuild's wall time.  RtError
+        (RT_ERR_STATE) before the first update."""
+        u = UpdateStats()
+        _check(lib.rt_update_info(self._ctx, ctypes.byref(u)), self._ctx)
+        return {k: getattr(u, k) for k, _ in UpdateStats._fields_ if k != "reserved"}
 
     def set_seeds(self, seeds):
         s = np.ascontiguousarray(seeds, dtype=np.uint32)

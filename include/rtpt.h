@@ -505,6 +505,56 @@ int rt_debug_tri_bvh(const rt_ctx* ctx, rt_tri_bvh_dump* dump);
  * for that bound to get the tree in one call. */
 int rt_debug_tri_bvh_host(const rt_scene_desc* scene, const rt_create_options* opt, rt_tri_bvh_dump* dump);
 
+/* ---- in-place scene updates ---------------------------------
+ * Added without a change of RTPT_ABI_VERSION: a caller detects them by the
+ * presence of the symbol rt_update_scene (dlsym). */
+#define RT_UPDATE_REBUILD 0x1u   /* rebuild the triangle BVH with the context's builder instead of refitting it */
+
+/* Replace the scene of a context.  `scene` is a whole rt_scene_desc with the
+ * same n_triangles, n_spheres, camera resolution and device as the context was
+ * created with; everything else may differ (camera pose, materials, light,
+ * vertices, spheres).  Afterwards every call on the context returns what a
+ * context newly created from `scene` with the same rt_create_options returns,
+ * bit for bit; only speed may differ.  Seeds are kept.  The running sum of
+ * RT_KEEP_SUM is dropped (accumulate=1 is RT_ERR_STATE until a new RT_KEEP_SUM
+ * call).  Synchronous; no other call on the context may be in flight.
+ *
+ * The triangle BVH keeps its topology and gets new boxes from a refit on the
+ * device (rt_refit.hip) when the context has a tree and the new scene still
+ * needs one; otherwise, or with RT_UPDATE_REBUILD, the update does what
+ * rt_create does (build one with the context's builder, or free it).  The
+ * refit keeps one table per context, made on the first refit and freed by
+ * rt_destroy: the parent entry and an arrival counter of every entry of the 8
+ * layouts, 2 x 4 B x 8 = 64 B per node of a layout.
+ *
+ * Failures: RT_ERR_INVALID_ARG (a null pointer, a changed count, resolution or
+ * device, an unknown flag bit, a scene the compile rejects) names the field in
+ * rt_last_error and leaves the context exactly as it was.  A device failure
+ * halfway (RT_ERR_OUT_OF_MEMORY, RT_ERR_LAUNCH) marks the context: every
+ * render, query and tree dump on it returns RT_ERR_STATE with a message until
+ * an rt_update_scene succeeds; no half-updated scene is ever read.
+ * rt_set_seeds, rt_fill_seeds, rt_denoise and rt_destroy keep working. */
+int rt_update_scene(rt_ctx* ctx, const rt_scene_desc* scene, uint32_t flags);
+
+typedef struct rt_update_stats {
+    uint32_t tri_bvh;      /* 0: the context has no triangle BVH, 1: refitted, 2: rebuilt */
+    uint32_t updates;      /* successful updates of this context so far */
+    float compile_ms;      /* host scene compile (wall) */
+    float upload_ms;       /* record upload (wall, sync included) */
+    float tri_bvh_ms;      /* refit: device time of its kernels (hipEvents); rebuild: wall */
+    float total_ms;        /* the whole call (wall) */
+    uint32_t reserved[2];  /* 0 */
+} rt_update_stats; /* 32 B */
+/* The last successful update.  RT_ERR_STATE (with a message) before the first. */
+int rt_update_info(const rt_ctx* ctx, rt_update_stats* info);
+
+/* rt_debug_tri_bvh_host(built_from, opt), then the refit onto `updated`'s triangles
+ * (same n_triangles, else RT_ERR_INVALID_ARG) with `updated`'s margin: what a context
+ * created with RT_TRI_BVH_HOST_SAH from `built_from` holds after rt_update_scene(updated).
+ * Host-only, no device: the refit is restated in plain C++ (rt_scene.cpp refit_tri_bvh). */
+int rt_debug_tri_bvh_refit_host(const rt_scene_desc* built_from, const rt_create_options* opt,
+                                const rt_scene_desc* updated, rt_tri_bvh_dump* dump);
+
 /* Self-check of the kernels' short correctly rounded sqrt and reciprocal
  *  against the IEEE expansions on every one of the 2^32 float
  * bit patterns, on the current device: mismatches[0] sqrt, [1] reciprocal

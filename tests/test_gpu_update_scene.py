@@ -1,0 +1,357 @@
+"""GPU: rt_update_scene.  After an update a context must return what a context
+newly created from the updated scene returns, bit for bit; the triangle BVH
+keeps its topology and gets its boxes from the device refit (rt_refit.hip).
+
+  1  identity    a refit onto unchanged triangles leaves the tree's bytes as
+                 every builder wrote them, and A -> shuffle -> A returns to them
+  2  moved       the refitted trees pass the node-by-node checker
+                 (tests/tri_bvh_tree.py), keep perm and the escape / leaf words,
+                 and for the host builders equal the host restatement of the
+                 refit (Scene.tri_bvh_refit_host) byte for byte
+  3  queries     sets B, C, E, G of tests/ray_sets.py, taken for the updated
+                 scene, equal the numpy scan of the updated scene
+  4  renders     equal the CPU oracle's render of the updated scene, with the
+                 seeds set before the update; the kernel is the one a fresh
+                 context launches; aov, ray queries and the MIS integrator
+                 equal a fresh context's
+  5  rebuild     RT_UPDATE_REBUILD gives a fresh context's tree
+  6  state       the running sum is dropped, argument errors name the field
+                 and leave the old scene in place, update_info counts successes
+
+The scenes are those of tests/update_scenes.py at the 40 x 24 frames of
+tests/tri_bvh_scenes.py."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import oracle_lib
+import ray_sets as rs
+import tri_bvh_scenes as ts
+import tri_bvh_tree as tt
+import update_scenes as us
+from gpuraytracer_amd import (CameraGPU, MisParams, Options, RenderParams, Renderer, RtError, Scene, SphereGPU,
+                              _native, lib, seed_splitmix)
+from test_gpu_parity import assert_parity
+from test_gpu_tri_bvh_tree import BUILDERS, context
+
+pytestmark = pytest.mark.gpu
+
+IDENTITY = ["tiny1", "tiny2", "tiny3", "soup385", "soup1025", "grid", "same600", "far", "past_half"]
+MOVED_SCENES = ["soup385", "soup1025", "grid", "same600", "far"]
+ARRAYS = ("nodes", "sorted", "perm", "isect")
+INVALID_ARG, STATE = 1, 5
+
+
+def assert_same_dump(got, want, what, keys=ARRAYS):
+    assert got["nodes_per_layout"] == want["nodes_per_layout"] and got["leaf_max"] == want["leaf_max"], what
+    assert np.float32(got["margin"]).tobytes() == np.float32(want["margin"]).tobytes(), (what, got["margin"], want["margin"])
+    for k in keys:
+        if got[k].tobytes() != want[k].tobytes():
+            bad = np.argwhere(got[k].view(np.uint32) != want[k].view(np.uint32))[0]
+            raise AssertionError(f"{what}: {k} differs first at {tuple(int(v) for v in bad)}")
+
+
+# ---- 1: identity -------------------------------------------------------------------
+
+@pytest.mark.parametrize("builder", list(BUILDERS))
+@pytest.mark.parametrize("name", IDENTITY)
+def test_refit_onto_the_same_triangles_keeps_every_byte(name, builder):
+    with context(name, builder) as r:
+        before = r.tri_bvh()
+        info = r.build_info()
+        r.update_scene(us.build(name, "same"))
+        assert r.update_info()["tri_bvh"] == 1
+        assert_same_dump(r.tri_bvh(), before, f"{name} {builder} same")
+        r.update_scene(us.build(name, "shuffle"))
+        r.update_scene(us.build(name, "same"))
+        assert_same_dump(r.tri_bvh(), before, f"{name} {builder} shuffle and back")
+        u = r.update_info()
+        assert u["tri_bvh"] == 1 and u["updates"] == 3, u
+        after = r.build_info()
+        assert (after["tri_bvh_build"], after["tri_bvh_nodes"]) == (info["tri_bvh_build"], info["tri_bvh_nodes"])
+
+
+# ---- 2: moved trees -----------------------------------------------------------------
+
+def check_refitted(r, name, kind, builder, before):
+    d = r.tri_bvh()
+    what = f"{name} {builder} {kind}"
+    tt.check(d, expect_nodes=r.build_info()["tri_bvh_nodes"])
+    assert d["perm"].tobytes() == before["perm"].tobytes(), what
+    assert d["nodes"][..., 3].tobytes() == before["nodes"][..., 3].tobytes(), what + ": an escape or leaf word changed"
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def fresh_isect(name, kind):
+    d = us.build(name, kind).tri_bvh_host()
+    return d["isect"].tobytes(), np.float32(d["margin"]).tobytes()
+
+
+@pytest.mark.parametrize("builder", list(BUILDERS))
+@pytest.mark.parametrize("name", MOVED_SCENES)
+def test_refit_onto_moved_triangles(name, builder):
+    opt = ts.options(name, **BUILDERS[builder])
+    with context(name, builder) as r:
+        before = r.tri_bvh()
+        for kind in us.MOVED:
+            r.update_scene(us.build(name, kind))
+            assert r.update_info()["tri_bvh"] == 1
+            d = check_refitted(r, name, kind, builder, before)
+            isect, margin = fresh_isect(name, kind)  # the scene compile is the same for every builder
+            assert d["isect"].tobytes() == isect and np.float32(d["margin"]).tobytes() == margin, (name, kind)
+            if builder.startswith("host"):
+                assert_same_dump(d, ts.build(name).tri_bvh_refit_host(us.build(name, kind), opt), f"{name} {builder} {kind}")
+
+
+@pytest.mark.parametrize("builder", ["host", "lbvh", "gpusah_leaf4"])
+def test_refit_over_many_workgroups(builder):
+    """soup20k: 79 workgroups a layout, the boxes go from one to the other through the counters."""
+    with context("soup20k", builder) as r:
+        before = r.tri_bvh()
+        for kind in ("shift", "shuffle"):
+            r.update_scene(us.build("soup20k", kind))
+            check_refitted(r, "soup20k", kind, builder, before)
+
+
+@pytest.mark.parametrize("builder", list(BUILDERS))
+@pytest.mark.parametrize("name", ["tiny1", "tiny2", "tiny3"])
+def test_refit_of_the_smallest_trees(name, builder):
+    with context(name, builder) as r:
+        before = r.tri_bvh()
+        r.update_scene(us.build(name, "grow"))
+        check_refitted(r, name, "grow", builder, before)
+
+
+# ---- 3: queries ---------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def query_sets(name, kind):
+    """[(which, rays)] for the updated scene: its ray domain (E) and its box faces (G)."""
+    scene = us.build(name, kind)
+    B, C = rs.sets_bc()
+    return (("B", B), ("C", C), ("E", rs.set_e(B, scene.ray_domain())), ("G", rs.set_g(scene)[0]))
+
+
+@functools.lru_cache(maxsize=None)
+def query_references(name, kind):
+    sets = [rays for _, rays in query_sets(name, kind)]
+    cuts = np.cumsum([len(s) for s in sets])[:-1]
+    sc, rays = rs.np_scene(us.build(name, kind)), np.concatenate(sets)
+    out = {}
+    for any_hit in (False, True):
+        t, ids = rs.reference(sc, rays, any_hit)
+        for (which, _), t_, i_ in zip(query_sets(name, kind), np.split(t, cuts), np.split(ids, cuts)):
+            out[which, any_hit] = (t_, i_)
+    return out
+
+
+@pytest.mark.parametrize("builder", ["host", "lbvh", "gpusah", "gpusah_leaf4"])
+@pytest.mark.parametrize("kind", ["shift", "shuffle"])
+@pytest.mark.parametrize("name", ["soup385", "grid", "far"])
+def test_queries_after_the_update_equal_the_scan(name, kind, builder):
+    with context(name, builder) as r:
+        r.update_scene(us.build(name, kind))
+        for which, rays in query_sets(name, kind):
+            for any_hit in (False, True):
+                got = r.trace_rays(rays, any_hit=any_hit)
+                want = query_references(name, kind)[which, any_hit]
+                assert rs.same(got, want), f"{name} {kind} {builder} {which} any={any_hit}: " + rs.first_difference(got, want)
+                kernel = r.last_launch()["kernel"]
+                assert kernel == f"rt::ray_query_kernel<5, false, {'true' if any_hit else 'false'}>", kernel
+
+
+# ---- 4: renders ---------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def oracle_frame(name, kind):
+    out = oracle_lib.render(us.build(name, kind), seed_splitmix(ts.W, ts.H), 2, 3)
+    out.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("builder", ["host", "lbvh", "gpusah"])
+@pytest.mark.parametrize("kind", ["shift", "shuffle"])
+@pytest.mark.parametrize("name", ["grid", "cell", "far", "same600"])
+def test_render_after_the_update_equals_the_oracle(name, kind, builder):
+    with Renderer(ts.build(name), seeds=seed_splitmix(ts.W, ts.H), options=ts.options(name, **BUILDERS[builder])) as r:
+        r.update_scene(us.build(name, kind))
+        out = r.render(RenderParams(spp=2, bounces=3))
+    assert_parity(out, oracle_frame(name, kind), f"{name} {kind} {builder}")
+
+
+def cornell_edit(w, h, break_pairs=False):
+    """The Cornell box with the camera moved, the back wall recoloured and the
+    short box (triangles 22-33) translated; ``break_pairs``: one vertex of a
+    box triangle moved by itself, so that no shared-edge pair layout exists."""
+    base = Scene.cornell_box(w, h)
+    tri = np.frombuffer(bytes(base.vertices), np.float32).reshape(-1, 3, 4)[:, :, :3].copy()
+    tri[22:34] += np.array([-0.25, 0.0, 0.125], np.float32)
+    if break_pairs:
+        tri[23, 0] += np.array([0.0, 0.03125, 0.0], np.float32)
+    cam = us.moved_camera(base.camera, eye=(0.5, 0.25, 8.0), look_at=(0.0, -0.25, -2.5))
+    s = us.with_vertices(base, tri, cam)
+    s.materials = us.recolored(base, (0, 1), (0.2, 0.3, 0.8))
+    return s
+
+
+@pytest.mark.parametrize("break_pairs", [False, True])
+def test_cornell_edit_renders_as_a_fresh_context(break_pairs):
+    w = h = 16
+    seeds = seed_splitmix(w, h)
+    edit = cornell_edit(w, h, break_pairs)
+    want = oracle_lib.render(edit, seeds, 2, 3)
+    with Renderer(edit, seeds=seeds) as f:
+        fresh = f.render(RenderParams(spp=2, bounces=3))
+        fresh_kernel = f.last_launch()
+        fresh_aov = f.render_aov(spp=2)
+    assert_parity(fresh, want, "fresh context")
+    with Renderer(Scene.cornell_box(w, h), seeds=seeds) as r:
+        r.render(RenderParams(spp=2, bounces=3))
+        old_kernel = r.last_launch()["kernel"]
+        r.update_scene(edit)
+        assert r.update_info()["tri_bvh"] == 0
+        out = r.render(RenderParams(spp=2, bounces=3))
+        assert r.last_launch() == fresh_kernel
+        aov = r.render_aov(spp=2)
+    assert_parity(out, want, f"cornell edit, pairs broken: {break_pairs}")
+    assert (fresh_kernel["kernel"] != old_kernel) == break_pairs, (old_kernel, fresh_kernel["kernel"])
+    for k in fresh_aov:
+        assert aov[k].tobytes() == fresh_aov[k].tobytes(), k
+
+
+def test_moved_spheres_render_as_the_oracle():
+    w = h = 16
+    seeds = seed_splitmix(w, h)
+    base = Scene.random_spheres(w, h, 60)
+    sph = (SphereGPU * 60)()
+    ctypes.memmove(ctypes.addressof(sph), ctypes.addressof(base.spheres), 60 * 80)
+    rng = np.random.default_rng(4)
+    for k in range(60):
+        dx, dy, dz = (float(v) for v in rng.uniform(-0.3, 0.3, 3).astype(np.float32))
+        sph[k].center.x += dx
+        sph[k].center.y += dy
+        sph[k].center.z += dz
+    moved = Scene(us.moved_camera(base.camera, eye=(0.3, 0.2, 8.5), look_at=(0.0, 0.0, -2.5)), base.materials,
+                  base.vertices, base.light, sph)
+    with Renderer(base, seeds=seeds) as r:
+        r.update_scene(moved)
+        out = r.render(RenderParams(spp=2, bounces=3))
+        rays = rs.sets_bc()[0][:512]
+        got = r.trace_rays(rays)
+    assert_parity(out, oracle_lib.render(moved, seeds, 2, 3), "moved spheres")
+    with Renderer(moved, seeds=seeds) as f:
+        assert rs.same(got, f.trace_rays(rays))
+
+
+def test_aov_rays_and_mis_after_the_update_equal_a_fresh_context():
+    """A BVH scene for the feature buffers and the queries, the MIS Cornell box at 16 x 12 for rt_render_mis."""
+    name, kind = "grid", "shift"
+    rays = rs.sets_bc()[0][:1024]
+    opt = ts.options(name, tri_build="gpusah")
+    seeds = seed_splitmix(ts.W, ts.H)
+    with Renderer(us.build(name, kind), seeds=seeds, options=opt) as f:
+        want_aov, want_center = f.render_aov(spp=2), f.render_aov(center=True)
+        want_hits = [f.trace_rays(rays, any_hit=a) for a in (False, True)]
+    with Renderer(ts.build(name), seeds=seeds, options=opt) as r:
+        r.update_scene(us.build(name, kind))
+        got_aov, got_center = r.render_aov(spp=2), r.render_aov(center=True)
+        got_hits = [r.trace_rays(rays, any_hit=a) for a in (False, True)]
+    for want, got in ((want_aov, got_aov), (want_center, got_center)):
+        for k in want:
+            assert got[k].tobytes() == want[k].tobytes(), k
+    for want, got in zip(want_hits, got_hits):
+        assert rs.same(got, want), rs.first_difference(got, want)
+
+    base = Scene.cornell_box_mis(16, 12)
+    tri = np.frombuffer(bytes(base.vertices), np.float32).reshape(-1, 3, 4)[:, :, :3].copy()
+    tri[22:34] += np.array([-0.25, 0.0, 0.125], np.float32)
+    edit = us.with_vertices(base, tri, us.moved_camera(base.camera, eye=(0.5, 0.25, 8.0), look_at=(0.0, -0.25, -2.5)))
+    p = MisParams(camera_rays=2, mis_samples=6)
+    with Renderer(edit) as f:
+        want = f.render_mis(p)
+    with Renderer(base) as r:
+        r.update_scene(edit)
+        got = r.render_mis(p)
+    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+
+
+# ---- 5: RT_UPDATE_REBUILD -------------------------------------------------------------
+
+@pytest.mark.parametrize("builder", ["host", "lbvh", "gpusah", "gpusah_leaf4"])
+def test_rebuild_gives_a_fresh_contexts_tree(builder):
+    name, kind = "soup1025", "shuffle"
+    opt = ts.options(name, **BUILDERS[builder])
+    with Renderer(us.build(name, kind), options=opt) as f:
+        want, want_info = f.tri_bvh(), f.build_info()
+    with context(name, builder) as r:
+        r.update_scene(us.build(name, kind))          # a refit first: the rebuild must drop its table with the tree
+        before = r.build_info()
+        r.update_scene(us.build(name, kind), rebuild=True)
+        assert_same_dump(r.tri_bvh(), want, f"{name} {builder} rebuild")
+        u, info = r.update_info(), r.build_info()
+        assert u["tri_bvh"] == 2 and u["updates"] == 2, u
+        assert (info["tri_bvh_build"], info["tri_bvh_nodes"]) == (want_info["tri_bvh_build"], want_info["tri_bvh_nodes"])
+        assert info["tri_bvh_build_ms"] > 0 and info["tri_bvh_build_ms"] != before["tri_bvh_build_ms"]
+        r.update_scene(us.build(name, "shift"))       # and a refit of the rebuilt tree
+        assert r.update_info()["tri_bvh"] == 1
+        tt.check(r.tri_bvh(), expect_nodes=info["tri_bvh_nodes"])
+
+
+# ---- 6: state and errors --------------------------------------------------------------
+
+def test_the_running_sum_is_dropped():
+    seeds = seed_splitmix(ts.W, ts.H)
+    with Renderer(ts.build("grid"), seeds=seeds, options=ts.options("grid")) as r:
+        r.accumulate(RenderParams(spp=1, bounces=3))
+        r.render(RenderParams(spp=1, bounces=3, sample_base=1, accumulate=True))  # the sum is there
+        r.update_scene(us.build("grid", "shift"))
+        with pytest.raises(RtError) as e:
+            r.render(RenderParams(spp=1, bounces=3, sample_base=1, accumulate=True))
+        assert e.value.status == STATE
+        r.accumulate(RenderParams(spp=1, bounces=3))
+        out = r.render(RenderParams(spp=1, bounces=3, sample_base=1, accumulate=True))
+    assert_parity(out, oracle_frame("grid", "shift"), "sum after the update")
+
+
+def test_argument_errors_leave_the_old_scene():
+    name = "grid"
+    base = ts.build(name)
+    seeds = seed_splitmix(ts.W, ts.H)
+    old = oracle_lib.render(base, seeds, 2, 3)
+    other_count = ts.build("soup385")
+    with_sphere = Scene(base.camera, base.materials, base.vertices, base.light, Scene.random_spheres(8, 8, 1).spheres)
+    cam = CameraGPU.from_buffer_copy(bytes(base.camera))
+    cam.resolution.x += 8
+    other_size = Scene(cam, base.materials, base.vertices, base.light)
+    nan_cam = CameraGPU.from_buffer_copy(bytes(base.camera))
+    nan_cam.position.x = float("nan")
+    rejected = Scene(nan_cam, base.materials, base.vertices, base.light)
+    with Renderer(base, seeds=seeds, options=ts.options(name)) as r:
+        with pytest.raises(RtError) as e:
+            r.update_info()
+        assert e.value.status == STATE and len(str(e.value)) > len("RT_ERR_STATE: ")
+        cases = [(other_count.desc(), 0, "n_triangles"), (with_sphere.desc(), 0, "n_spheres"),
+                 (other_size.desc(), 0, "resolution"), (base.desc(device=1), 0, "device"),
+                 (us.build(name, "shift").desc(), 0x2, "flags"), (us.build(name, "shift").desc(), 0x80000001, "flags"),
+                 (rejected.desc(), 0, "camera")]
+        for desc, flags, field in cases:
+            assert lib.rt_update_scene(r._ctx, ctypes.byref(desc), flags) == INVALID_ARG, field
+            assert field in lib.rt_last_error(r._ctx).decode(), (field, lib.rt_last_error(r._ctx))
+            assert_parity(r.render(RenderParams(spp=2, bounces=3)), old, f"after a refused update ({field})")
+        assert lib.rt_update_scene(r._ctx, None, 0) == INVALID_ARG and b"scene" in lib.rt_last_error(r._ctx)
+        no_cam = base.desc()
+        no_cam.camera = None
+        assert lib.rt_update_scene(r._ctx, ctypes.byref(no_cam), 0) == INVALID_ARG and b"camera" in lib.rt_last_error(r._ctx)
+        with pytest.raises(RtError):
+            r.update_info()  # nothing succeeded yet
+        r.update_scene(us.build(name, "shift"))
+        assert r.update_info()["updates"] == 1
+        with pytest.raises(RtError):
+            r.update_scene(other_count)
+        assert r.scene is not other_count and r.update_info()["updates"] == 1
+        assert_parity(r.render(RenderParams(spp=2, bounces=3)), oracle_frame(name, "shift"), "after the update")
+        u = r.update_info()
+        assert u["compile_ms"] > 0 and u["upload_ms"] > 0 and u["tri_bvh_ms"] > 0 and u["total_ms"] >= u["compile_ms"]

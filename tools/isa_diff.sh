@@ -19,7 +19,7 @@ T=$(mktemp -d)
 trap 'git -C "$R" worktree remove --force "$T/rev" >/dev/null 2>&1 || true; rm -rf "$T"' EXIT
 git -C "$R" worktree add --detach "$T/rev" "$1" >/dev/null
 CC=$(make -s -C "$R" --eval 'isa-cc: ; @echo $(HIPCC) $(HIPFLAGS)' isa-cc)
-FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_aov rt_denoise rt_mathcheck"
+FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_refit rt_aov rt_denoise rt_mathcheck"
 mkdir -p "$T/new" "$T/old"
 export T CC
 for f in $FILES; do
