@@ -14,7 +14,11 @@ HOSTCXX ?= /opt/rocm/llvm/bin/clang++
 HIPFLAGS := $(COMMON) --offload-arch=$(ARCH) -fno-slp-vectorize $(EXTRA)
 HOSTFLAGS := $(COMMON) -D__HIP_PLATFORM_AMD__ -isystem /opt/rocm/include $(EXTRA)
 
-OBJS := $(BLD)/rt_kernel.o $(BLD)/rt_rays.o $(BLD)/rt_aov.o $(BLD)/rt_denoise.o $(BLD)/rt_mis.o $(BLD)/rt_lbvh.o $(BLD)/rt_gsah.o $(BLD)/rt_refit.o $(BLD)/rt_mathcheck.o $(BLD)/rt_api.o $(BLD)/rt_scene.o $(BLD)/rt_image.o
+# The library's objects, named once: the device ones (.hip) and the host ones
+# (.cpp), which the sanitizer build below compiles a second time.
+DEV_OBJS := rt_kernel.o rt_rays.o rt_aov.o rt_denoise.o rt_mis.o rt_lbvh.o rt_gsah.o rt_refit.o rt_mathcheck.o
+HOST_OBJS := rt_api.o rt_api_host.o rt_scene.o rt_image.o
+OBJS := $(addprefix $(BLD)/,$(DEV_OBJS) $(HOST_OBJS))
 HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp
 
 LIB ?= $(PKG)/librtpt.so
@@ -34,7 +38,8 @@ $(BLD)/%.o: $(SRC)/%.hip $(HDRS) $(SRC)/rt_trace.hpp | $(BLD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the device-vs-host check of the shared scalar functions
-$(BLD)/rt_mathcheck.o $(BLD)/rt_image.o: $(SRC)/rt_half.h $(SRC)/rt_mathcheck.hpp
+$(BLD)/rt_mathcheck.o $(BLD)/rt_image.o $(BLD)/rt_api_host.o: $(SRC)/rt_half.h $(SRC)/rt_mathcheck.hpp
+$(BLD)/rt_api_host.o: $(SRC)/rt_api_internal.hpp
 
 $(BLD)/rt_api.o: $(SRC)/rt_api.cpp $(ALLSRC) | $(BLD)
 	$(HOSTCXX) $(HOSTFLAGS) -DRT_SRC_SHA='"$(SRC_SHA)"' -c $< -o $@
@@ -62,7 +67,7 @@ oracle:
 ASAN := build_asan
 SAN := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -g -shared-libasan
 ASAN_RT := $(shell $(HOSTCXX) -print-file-name=libclang_rt.asan-x86_64.so)
-ASAN_HOST := $(ASAN)/rt_api.o $(ASAN)/rt_scene.o $(ASAN)/rt_image.o
+ASAN_HOST := $(addprefix $(ASAN)/,$(HOST_OBJS))
 
 $(ASAN):
 	mkdir -p $(ASAN)
@@ -73,9 +78,10 @@ $(ASAN)/rt_api.o: $(SRC)/rt_api.cpp $(ALLSRC) | $(ASAN)
 $(ASAN)/%.o: $(SRC)/%.cpp $(HDRS) | $(ASAN)
 	$(HOSTCXX) $(HOSTFLAGS) $(SAN) -c $< -o $@
 
-$(ASAN)/rt_image.o: $(SRC)/rt_half.h
+$(ASAN)/rt_image.o $(ASAN)/rt_api_host.o: $(SRC)/rt_half.h
+$(ASAN)/rt_api_host.o: $(SRC)/rt_api_internal.hpp $(SRC)/rt_mathcheck.hpp
 
-$(ASAN)/librtpt.so: $(ASAN_HOST) $(BLD)/rt_kernel.o $(BLD)/rt_rays.o $(BLD)/rt_aov.o $(BLD)/rt_denoise.o $(BLD)/rt_mis.o $(BLD)/rt_lbvh.o $(BLD)/rt_gsah.o $(BLD)/rt_refit.o $(BLD)/rt_mathcheck.o
+$(ASAN)/librtpt.so: $(ASAN_HOST) $(addprefix $(BLD)/,$(DEV_OBJS))
 	$(HOSTCXX) -shared $(SAN) -o $@ $^ -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
 
 $(ASAN)/liboracle.so: oracle/pt_oracle.c oracle/pt_oracle.h include/rt_types.h | $(ASAN)

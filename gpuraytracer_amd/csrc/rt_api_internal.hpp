@@ -1,0 +1,102 @@
+// rt_api_internal.hpp — what the two halves of the C-ABI share: rt_api.cpp
+// (every entry point that takes or makes an rt_ctx) and rt_api_host.cpp (the
+// entry points that need neither a context nor a stream).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/rtpt.h"
+#include "rt_kernel.hpp"
+#include "rt_scene.hpp"
+
+namespace rtapi {
+
+// RT_TRI_BVH_DEFAULT resolves to this build: the GPU binned SAH builds the host
+// build's tree (same rules, same render rate) in a tenth of the time or less --
+// the measured build times and rates are in DESIGN.md §5 and profiles/
+constexpr uint32_t kDefaultTriBuild = RT_TRI_BVH_GPU_SAH;
+
+// The message goes to the context, or without one to the calling thread's
+// create-error slot (rt_last_error(NULL)); rt_api.cpp holds both.
+int fail(rt_ctx* ctx, int status, const std::string& msg);
+
+inline int hip_fail(rt_ctx* ctx, int status, const char* what, hipError_t e) {
+    return fail(ctx, status, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// rt_create_options (include/rtpt.h) -> the context's choices and the host
+// builds' options.  False (with *why) for a value outside its range.
+struct Resolved {
+    uint32_t lanes = 0, tri_build = RT_TRI_BVH_HOST_SAH, walk = RT_WALK_AUTO, walk_leaf_den = 0;
+    rt::SceneMem mem = rt::SceneMem::kAuto;
+    uint32_t tri_leaf_max = rt::kTriLeafMax;
+    double tri_leaf_cost = 1.0;
+    rt::BuildOptions build;
+};
+bool resolve_options(const rt_create_options* o, Resolved* r, const char** why);
+
+// A scene description that compile_desc may read (n_square_lights is the
+// business of the entry points that create or update a context).
+inline bool desc_ok(const rt_scene_desc* d) { return d && d->camera && d->square_lights; }
+
+inline bool compile_desc(const rt_scene_desc* d, const rt::BuildOptions& build, rt::CompiledScene* s,
+                         const char** err) {
+    return rt::compile_scene(*d->camera, d->materials, d->vertices, d->n_triangles, d->square_lights[0], d->spheres,
+                             d->n_spheres, s, err, build);
+}
+
+// The counts of a compiled scene's tables (rt_kernel.hpp SceneTables), which
+// every layout choice is made from; the pointers stay null.
+// nTN: triangle-BVH nodes per layout (0: none).
+inline rt::SceneTables scene_counts(const rt::CompiledScene& s, uint32_t nTN) {
+    rt::SceneTables t{};
+    t.nT = (uint32_t)s.tri_isect.size();
+    t.nP = (uint32_t)s.pair_isect.size();
+    t.nS = (uint32_t)s.sph_isect.size();
+    t.nN = s.sph_layout_nodes;
+    t.nTN = nTN;
+    t.nC = (uint32_t)(s.clusters.size() / (4 * rt::kCluF4));
+    t.pair_free = s.pair_free_mask;
+    return t;
+}
+
+// rt_create's rule: a triangle BVH above kTriBvhMinTriangles or when the
+// records do not fit the LDS layouts, or when the layout is forced.
+inline bool needs_tri_bvh(const rt::SceneTables& t, rt::SceneMem mem) {
+    const size_t lds_pairs = rt::kernel_lds_bytes(t.nT, t.nP, 0, 0);
+    const size_t lds_single = rt::kernel_lds_bytes(t.nT, 0, 0, 0);
+    return t.nT > 0 && (mem == rt::SceneMem::kTriBvh ||
+                        (mem == rt::SceneMem::kAuto &&
+                         (t.nT > rt::kTriBvhMinTriangles || std::min(lds_pairs, lds_single) > rt::kMaxLdsBytes)));
+}
+
+// The SAH builds clamp rt_create_options.tri_leaf_max to 1..128.
+inline uint32_t tri_leaf_clamp(uint32_t leaf_max) { return std::min(128u, std::max(1u, leaf_max)); }
+
+inline size_t pixel_bytes(uint32_t flags) { return (flags & RT_OUT_RGBA8) ? 4u : (flags & RT_OUT_FP16) ? 8u : 16u; }
+
+// Row layout of the gather (rt_tile_layout): rank k of N owns the frame rows
+// y = k + j*N, j < rows; every rank sends a tile padded to rows_max rows, so
+// the gathered buffer holds N tiles of tile_bytes back to back.  A rank past
+// the last row (N > H) owns no row and sends its padded tile all the same.
+struct TileLayout {
+    uint32_t rows, rows_max;
+    size_t row_bytes, tile_bytes;
+};
+
+inline TileLayout tile_layout(uint32_t W, uint32_t H, uint32_t N, uint32_t rank, uint32_t flags) {
+    TileLayout L;
+    L.rows = rank < H ? (H - 1u - rank) / N + 1u : 0u;
+    L.rows_max = (H + N - 1u) / N;
+    L.row_bytes = (size_t)W * pixel_bytes(flags);
+    L.tile_bytes = (size_t)L.rows_max * L.row_bytes;
+    return L;
+}
+
+// halton(i, d) of the SwiftPM kernel (Sources/gpuRaytracer/shaders.metal:32-47),
+// the same loop as RTrace/sampling.metal:107-122.
+float halton_host(uint32_t i, uint32_t d);
+
+}  // namespace rtapi

@@ -1,7 +1,7 @@
 // rt_beam.hpp — which pair records the camera rays of a pixel rectangle can hit
 // (DESIGN.md §3.16).  One source text for the gfx950 kernel (rt_kernel.hip: the
 // per-wave candidate mask of the bounce-0 closest query) and for the host
-// (rt_api.cpp rt_debug_camera_candidates, the CPU tests).
+// (rt_api_host.cpp rt_debug_camera_candidates, the CPU tests).
 //
 // Every camera ray of the rectangle starts at the camera position and its
 // un-normalised direction (cu*sh + cv*th) - cw is affine in (sh, th), so the

@@ -1,11 +1,11 @@
 // rt_mathcheck.hpp — what rt_debug_math_values / rt_debug_math_sums evaluate
 // (include/rtpt.h): one definition of "function fn on input
-// pattern b", compiled for x86 into rt_api.cpp and for gfx950 into
+// pattern b", compiled for x86 into rt_api_host.cpp and for gfx950 into
 // rt_mathcheck.hip.  The two compiles differ only where the library's host
 // and device code differ: sqrt_cr / rcp_cr (rt_math.h) and the half
 // conversions (__float2half_rn / __half2float against rt_half.h).  The Halton
 // forms are device templates (rt_halton.hpp) and live in rt_mathcheck.hip; the
-// host has the reference loop of rt_api.cpp.
+// host has the reference loop of rt_api_host.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,7 +76,7 @@ constexpr uint32_t kMathChunkLog2Min = 6, kMathChunkLog2Max = 31;
 
 // Device side (rt_mathcheck.hip): host arrays in and out, the current device,
 // its null stream, synchronous.  The arguments were validated by the caller
-// (rt_api.cpp): fn below kMathFnCount, D < 24 (a table dimension for _TAB),
+// (rt_api_host.cpp): fn below kMathFnCount, D < 24 (a table dimension for _TAB),
 // indices of _SMALL / _TAB below math_small_index_max().
 bool math_dim_has_table(uint32_t D);
 uint32_t math_small_index_max();

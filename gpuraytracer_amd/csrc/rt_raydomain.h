@@ -1,6 +1,6 @@
 // rt_raydomain.h — the exactness domain of the batched ray queries
 // (DESIGN.md §3.20), written once for the gfx950 query kernel (rt_rays.hip)
-// and for the host (rt_api.cpp rt_debug_ray_domain).
+// and for the host (rt_api_host.cpp rt_debug_ray_domain).
 //
 // Every culling structure is padded by 4e-5 * extent, where extent is the
 // larger of the scene's extent and the camera's distance from the origin

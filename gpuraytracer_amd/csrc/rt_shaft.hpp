@@ -1,7 +1,7 @@
 // rt_shaft.hpp — which pair records the bounce-0 shadow rays of a pixel
 // rectangle can hit.  One source text for the gfx950 kernel
 // (rt_kernel.hip: the per-wave occluder mask of the bounce-0 shadow query) and
-// for the host (rt_api.cpp rt_debug_shadow_candidates, the CPU tests).
+// for the host (rt_api_host.cpp rt_debug_shadow_candidates, the CPU tests).
 //
 // The bounce-0 shadow segments of a wave start at the camera rays' hit points,
 // lifted by the shading normal, and end inside the light patch.  The hit
