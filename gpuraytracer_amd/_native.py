@@ -294,6 +294,8 @@ SIGNATURES = {
                                               ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "rt_debug_light_mask": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(ctypes.c_uint64), _P,
                                            ctypes.c_uint32]),
+    "rt_debug_halton_table": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _P, _P]),
+    "rt_debug_halton_table_device": (ctypes.c_int, [_P, _P, ctypes.c_uint32]),
 }
 
 

@@ -115,6 +115,7 @@ struct rt_ctx {
     rt::SceneTables tab{};           // what every kernel traces through: borrows the buffers above (finish_scene)
     bool sph_compact = false;        // rt_scene.hpp sphere_compact_usable: the sphere kernel's tables exist
     uint64_t light_mask = 0;         // rt_scene.hpp light_mask: the box-cluster kernel's light flags
+    DevBuf d_halton_tab;             // the Halton low-digit tables (rt_halton.hpp), filled once by rt_create_ex
     uint32_t tri_bvh_build_used = 0; // rt_tri_bvh_build of the built tree (0: none)
     uint32_t tri_leaf_max = 1;       // triangles per leaf at most in the built tree (rt_debug_tri_bvh)
     float tri_bvh_build_ms = 0.0f;   // wall time of the triangle-BVH build
@@ -456,6 +457,7 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     set_tables(&K, c->tab);
     K.tri_shade = c->d_scene[kTriShade].as<float4>();
     K.light_mask = c->light_mask;
+    K.halton_tab = c->d_halton_tab.as<float>();
     // both compact tables or neither: the launcher takes the sphere kernel when
     // sph_lds is set, and that kernel's walks read sph_box (finish_scene)
     K.sph_lds = c->sph_compact ? c->d_scene[kSphLds].as<uint32_t>() : nullptr;
@@ -938,6 +940,15 @@ int rt_create_ex(const rt_scene_desc* d, const rt_create_options* opt, rt_ctx** 
         if ((e = c->d_seeds.reserve(npx * sizeof(uint32_t))) != hipSuccess) {
             status = RT_ERR_OUT_OF_MEMORY; msg = std::string("hipMalloc(seeds): ") + hipGetErrorString(e); break;
         }
+        // the Halton low-digit tables: the same for every scene, made once per
+        // context and copied into LDS by the box-cluster kernel's workgroups
+        if ((e = c->d_halton_tab.resize_exact(sizeof(float) * rt::kHaltonTabLdsFloats)) != hipSuccess) {
+            status = RT_ERR_OUT_OF_MEMORY; msg = std::string("hipMalloc(halton tables): ") + hipGetErrorString(e); break;
+        }
+        if ((e = rt::launch_fill_halton_tables(c->d_halton_tab.as<float>(), c->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+            status = RT_ERR_LAUNCH; msg = std::string("halton tables: ") + hipGetErrorString(e); break;
+        }
     } while (0);
     if (status != RT_OK) {
         delete c;
@@ -1240,6 +1251,17 @@ int rt_debug_tri_bvh(const rt_ctx* c, rt_tri_bvh_dump* dump) {
         if (e != hipSuccess) return RT_ERR_LAUNCH;
     }
     return RT_OK;
+}
+
+int rt_debug_halton_table_device(const rt_ctx* c, float* table, uint32_t capacity) {
+    if (!c || !table) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    if (capacity < rt::kHaltonTabLdsFloats)
+        return fail(const_cast<rt_ctx*>(c), RT_ERR_INVALID_ARG, "rt_debug_halton_table_device: capacity below the table's size");
+    if (!c->d_halton_tab) return RT_ERR_STATE;
+    DeviceGuard g(c->device);
+    const hipError_t e =
+        hipMemcpy(table, c->d_halton_tab.as<void>(), sizeof(float) * rt::kHaltonTabLdsFloats, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? RT_OK : RT_ERR_LAUNCH;
 }
 
 int rt_last_launch(const rt_ctx* c, rt_launch_info* info) {

@@ -11,6 +11,7 @@
 
 #include "rt_api_internal.hpp"
 #include "rt_beam.hpp"
+#include "rt_halton.hpp"
 #include "rt_mathcheck.hpp"
 #include "rt_shaft.hpp"
 
@@ -350,6 +351,21 @@ int rt_debug_light_mask(const rt_scene_desc* d, uint64_t* mask, float* records, 
     *mask = rt::light_mask(s);
     for (size_t k = 0; k < s.tri_shade.size() && k < capacity_triangles; ++k)
         memcpy(records + 16 * k, s.tri_shade[k].s, sizeof(s.tri_shade[k].s));
+    return RT_OK;
+}
+
+int rt_debug_halton_table(float* table, uint32_t capacity, uint32_t* n_floats, uint32_t* offsets, uint32_t* sizes) {
+    static_assert(rt::kHaltonTabFloats == rt::kHaltonTabLdsFloats, "rt_kernel.hpp's size of the tables");
+    if (!n_floats || (!table && capacity)) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
+    *n_floats = rt::kHaltonTabFloats;
+    for (int D = 0; D < 24; ++D) {
+        if (offsets) offsets[D] = rt::tab_offset(D);
+        if (sizes) sizes[D] = rt::tab_size(D);
+    }
+    if (!table) return RT_OK;
+    if (capacity < rt::kHaltonTabFloats)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "rt_debug_halton_table: capacity below the table's size");
+    rt::fill_halton_tables(table, 0u, 1u);  // the kernels' fill as one thread of one
     return RT_OK;
 }
 

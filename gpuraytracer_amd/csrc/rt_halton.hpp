@@ -101,10 +101,14 @@ __device__ __forceinline__ float halton_small(uint32_t i) {
 
 // ---- low-digit tables --------------------------------------
 // The reference adds the digits lowest first, so after the k lowest digits its
-// running sum depends only on i mod b^k.  A workgroup fills T_D[v] (v < b^k,
-// the loop's r after k digit steps of v; digits past v's own add +0) in LDS
-// with the same fp32 operations, and halton_tab continues from T_D[i mod b^k]
-// with the remaining digits of i / b^k: the same sum, bit for bit.  k per
+// running sum depends only on i mod b^k.  T_D[v] (v < b^k, the loop's r after
+// k digit steps of v; digits past v's own add +0) is made with the same fp32
+// operations, and halton_tab continues from T_D[i mod b^k] with the remaining
+// digits of i / b^k: the same sum, bit for bit.  The tables depend on kPrimes
+// and kTabDigits alone: a context fills them once into device memory
+// (rt_kernel.hip halton_tables_kernel) and a workgroup of the box-cluster
+// kernel copies them into LDS (copy_halton_tables); the AOV kernel and the
+// math check fill their LDS copies in place.  k per
 // dimension fits the tables in ~18 KB of LDS (the camera jitter and bounces
 // 0-1; 24 of the 73 digit steps of a 3-bounce sample).
 // i / b^k and i mod b^k come from one float digit step with n = b^k (< 2^23).
@@ -120,8 +124,9 @@ constexpr float f_after(uint32_t b, int k) {
     return f;
 }
 
+// Host and device: rt_debug_halton_table (rt_api_host.cpp) runs it on the host.
 template <uint32_t D>
-__device__ __forceinline__ void fill_halton_table(float* tab, uint32_t tid, uint32_t nthreads) {
+RT_HD void fill_halton_table(float* tab, uint32_t tid, uint32_t nthreads) {
     constexpr uint32_t b = kPrimes[D];
     constexpr int k = kTabDigits[D];
     constexpr float invB = 1.0f / (float)b;
@@ -141,7 +146,7 @@ __device__ __forceinline__ void fill_halton_table(float* tab, uint32_t tid, uint
 }
 
 // All tables; every thread of the workgroup calls it (then a barrier).
-__device__ __forceinline__ void fill_halton_tables(float* tab, uint32_t tid, uint32_t nthreads) {
+RT_HD void fill_halton_tables(float* tab, uint32_t tid, uint32_t nthreads) {
     fill_halton_table<1>(tab, tid, nthreads);
     fill_halton_table<2>(tab, tid, nthreads);
     fill_halton_table<3>(tab, tid, nthreads);
@@ -153,6 +158,28 @@ __device__ __forceinline__ void fill_halton_tables(float* tab, uint32_t tid, uin
     fill_halton_table<10>(tab, tid, nthreads);
     static_assert(kHaltonTabFloats == 729 + 625 + 343 + 121 + 169 + 361 + 529 + 841 + 961,
                   "table list");
+}
+
+// The filled tables from device memory (src: kHaltonTabFloats floats, 16-byte
+// aligned, L2-resident: every workgroup reads the same 18.7 KB) into the
+// workgroup's LDS slots (tab: 16-byte aligned), as float4 with a scalar tail;
+// every thread of the workgroup calls it (then a barrier).  The loads of all
+// rounds are issued before the first LDS store.
+template <uint32_t NT>
+__device__ __forceinline__ void copy_halton_tables(float* tab, const float* __restrict__ src, uint32_t tid) {
+    constexpr uint32_t n4 = kHaltonTabFloats / 4u, tail = kHaltonTabFloats % 4u;
+    constexpr uint32_t rounds = (n4 + NT - 1u) / NT;
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+    float4* d4 = reinterpret_cast<float4*>(tab);
+    // the last round's lanes past the end re-read the last float4 (not stored):
+    // unconditional loads keep v[] in registers
+    float4 v[rounds];
+#pragma unroll
+    for (uint32_t k = 0; k < rounds; ++k) v[k] = s4[tid + k * NT < n4 ? tid + k * NT : n4 - 1u];
+#pragma unroll
+    for (uint32_t k = 0; k < rounds; ++k)
+        if (tid + k * NT < n4) d4[tid + k * NT] = v[k];
+    if (tid < tail) tab[4u * n4 + tid] = src[4u * n4 + tid];
 }
 
 // halton_small<D> for i < kSmallIndexMax starting from the low-digit table.

@@ -612,7 +612,8 @@ void path_trace_kernel(KParams P) {
             const uint32_t tab0 = n.rec + n.clu;
             const bool tab = halton_tables_on(GEO, SMALL, P.spp, L);
             sv.htab = tab ? reinterpret_cast<const float*>(lds + tab0) : nullptr;
-            if (tab) fill_halton_tables(reinterpret_cast<float*>(lds + tab0), threadIdx.x, NT);
+            // the context's tables (filled once, rt_create_ex): a copy, not a fill
+            if (tab) copy_halton_tables<NT>(reinterpret_cast<float*>(lds + tab0), P.halton_tab, threadIdx.x);
         }
         __syncthreads();
     }
@@ -727,7 +728,17 @@ void path_trace_kernel(KParams P) {
     }
     const f3 cu = ld_f3(P.cam_u), cv = ld_f3(P.cam_v), cw = ld_f3(P.cam_w);
     const float fW = (float)P.W, fH = (float)P.H;
-    const uint32_t rounds = (P.spp + (L - 1)) / L;
+    uint32_t rounds = (P.spp + (L - 1)) / L;
+    // A wave whose camera mask is empty hits nothing (the mask holds the free
+    // pairs too, and this form has no spheres): every sample adds (+0, +0, +0)
+    // to the pixel's sum.  It skips the sample loop and the epilogue adds +0
+    // once, which leaves the bits that spp such additions leave.
+    constexpr bool kDeadSkip = RT_CAM_CAND && RT_DEAD_SKIP && GEO == kGeoPairClu && !SPH;
+    bool dead = false;
+    if constexpr (kDeadSkip) {
+        dead = sv.cam_avail && sv.cam_mask == 0u;  // wave-uniform
+        if (dead) rounds = 0u;
+    }
     for (uint32_t r = 0; r < rounds; ++r) {                      // :34
 #ifdef RT_STATS
         const unsigned long long t_round = clock64();  // slot 24: cycles of whole rounds
@@ -819,6 +830,10 @@ void path_trace_kernel(KParams P) {
         if (t % L != 0) return;
         const uint32_t slot = t / L;
         lum = f3{lum_s[3 * slot], lum_s[3 * slot + 1], lum_s[3 * slot + 2]};
+    }
+    if constexpr (kDeadSkip) {
+        // x + (+0) once is x + (+0) spp times: only x == -0 changes, on the first
+        if (dead && P.spp != 0u) lum = lum + f3{0.0f, 0.0f, 0.0f};
     }
     uint32_t x, j;
     pixel_of(t, x, j);
@@ -915,6 +930,12 @@ __global__ void fill_seeds_kernel(uint32_t* seeds, uint64_t key, uint64_t n) {
         z = z ^ (z >> 31);
         seeds[p] = (uint32_t)(z & 0xFFFFFu);
     }
+}
+
+// The Halton low-digit tables of a context (KParams::halton_tab): one workgroup
+// runs the fill that every workgroup of the box-cluster kernel used to run.
+__global__ __launch_bounds__(kBlockThreads) void halton_tables_kernel(float* tab) {
+    fill_halton_tables(tab, threadIdx.x, kBlockThreads);
 }
 
 // Placement of the gathered row tiles (rt_render_gather / rt_place_tiles): one
@@ -1260,6 +1281,11 @@ hipError_t math_selfcheck(unsigned long long bad[2]) {
     }
     (void)hipFree(d);
     return e;
+}
+
+hipError_t launch_fill_halton_tables(float* tab, hipStream_t stream) {
+    hipLaunchKernelGGL(halton_tables_kernel, dim3(1), dim3(kBlockThreads), 0, stream, tab);
+    return hipGetLastError();
 }
 
 hipError_t launch_fill_seeds(uint32_t* seeds, uint64_t key, uint64_t n, hipStream_t stream) {

@@ -44,6 +44,19 @@ constexpr uint32_t kCluF4 = 7;   // float4 per box cluster (rt_scene.hpp Compile
 #ifndef RT_SHD_CAND
 #define RT_SHD_CAND 1
 #endif
+// An occluder mask of at most this many pairs is tested directly, pair by pair
+// on every lit lane, without the cluster filter (needs
+// RT_SHD_CAND); 0: every non-empty mask goes through the filter.  Measured at
+// 1, 2 and 3 (profiles/r19/ab_results.md): 3 covers 99.8 % of the decided
+// non-empty masks of the 1080p Cornell frame and ran fastest
+#ifndef RT_SHD_SHORT
+#define RT_SHD_SHORT 3
+#endif
+// A wave whose camera mask is empty skips the sample loop: its pixels' sums
+// get +0 once (needs RT_CAM_CAND); 0: the loop runs
+#ifndef RT_DEAD_SKIP
+#define RT_DEAD_SKIP 1
+#endif
 // Its closest queries of bounce >= 1 test each lane's entry-side candidates
 // first and the exit-side ones only where they can still win against the hit
 // found (rt_cluorder.hpp); 0: one candidate mask per lane in
@@ -131,6 +144,8 @@ struct KParams {
     uint32_t pair_free;       // pairs in no cluster (bit mask)
     uint64_t light_mask;      // box-cluster kernel: bit id set when triangle id is a light, i.e. its
                               // TriShade s0.w != 0 (ids < 64; rt_scene.hpp light_mask)
+    const float* halton_tab;  // box-cluster kernel: the context's Halton low-digit tables, kHaltonTabLdsFloats
+                              // floats (launch_fill_halton_tables), copied into LDS when halton_tables_on
 };
 
 size_t kernel_lds_bytes(uint32_t n_tri, uint32_t n_pairs, uint32_t n_sph, uint32_t n_nodes);
@@ -372,6 +387,9 @@ hipError_t refit_tri_bvh(const float4* d_tri, uint32_t n, float margin, uint4* d
 hipError_t refit_format_errors(const uint32_t* d_table, uint32_t total, uint32_t* bad);
 
 hipError_t launch_fill_seeds(uint32_t* seeds, uint64_t key, uint64_t n, hipStream_t stream);
+// The Halton low-digit tables (rt_halton.hpp fill_halton_tables) into `tab`,
+// kHaltonTabLdsFloats floats of device memory: once per context (rt_create_ex).
+hipError_t launch_fill_halton_tables(float* tab, hipStream_t stream);
 // The shipped short sqrt / reciprocal (rt_math.h sqrt_cr, rcp_cr) against IEEE
 // sqrtf and 1/x over every float on the current device: mismatch counts.
 hipError_t math_selfcheck(unsigned long long bad[2]);

@@ -1019,6 +1019,17 @@ __device__ __forceinline__ bool any_hit(const SceneView& sv, f3& o, f3& d, float
             // bounce-0 shadow rays: the wave's occluder mask (rt_shaft.hpp);
             // the boolean does not depend on which non-occluders are skipped
             if (sv.shd_mask == 0u) return false;
+            if (RT_SHD_SHORT > 0 && __builtin_popcount(sv.shd_mask) <= RT_SHD_SHORT) {
+                // a short mask (wave-uniform): its pairs tested directly on every
+                // lane, scalar k and same-address LDS reads, in place of the
+                // cluster filter that could only drop some of them; a lane
+                // stops at its first accepted hit
+                for (uint32_t m = sv.shd_mask; m != 0u && id < 0; m &= m - 1u) {
+                    const uint32_t k = (uint32_t)__builtin_ctz(m);
+                    pair_test_rank<true>(sv.pair + kPairF4 * k, k, o, d, tmin, &tm, &id);
+                }
+                return id >= 0;
+            }
             cluster_query<true, true, true>(sv, o, d, tmin, &tm, &id);
         } else {
             cluster_query<true, true, false, false, RT_CLU_LEAN != 0>(sv, o, d, tmin, &tm, &id);

@@ -752,6 +752,19 @@ int rt_debug_shadow_candidates(const rt_scene_desc* scene, int32_t x0, int32_t x
  * when capacity is 0); *n_clusters: how many the scene has (at most 31). */
 int rt_debug_cluster_kinds(const rt_scene_desc* scene, uint32_t* flags, uint32_t capacity, uint32_t* n_clusters);
 
+/* Debug (host-only): the Halton low-digit tables of the box-cluster kernel
+ * (gpuraytracer_amd/csrc/rt_halton.hpp), from the x86 compile
+ * of the header's fill: table[offsets[D] + v], v < sizes[D], is the reference
+ * loop's running sum after the tabulated digit steps of v in base primes[D];
+ * sizes[D] = 0 for a dimension without a table.  offsets and sizes hold 24
+ * words each (either may be null); table has room for capacity floats and may
+ * be null when capacity is 0 (*n_floats alone is then reported). */
+int rt_debug_halton_table(float* table, uint32_t capacity, uint32_t* n_floats, uint32_t* offsets, uint32_t* sizes);
+/* Debug: the same tables as the context's device buffer holds them (filled by
+ * a kernel in rt_create_ex, copied into LDS by every workgroup of a launch that
+ * has the tables on); capacity >= *n_floats of rt_debug_halton_table. */
+int rt_debug_halton_table_device(const rt_ctx* ctx, float* table, uint32_t capacity);
+
 /* Debug (host-only): the light mask the box-cluster kernel tests instead of
  * loading a hit triangle's light flag: bit id of *mask is set
  * when triangle id is a light (scenes of at most 64 triangles, else 0).
