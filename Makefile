@@ -16,10 +16,10 @@ HOSTFLAGS := $(COMMON) -D__HIP_PLATFORM_AMD__ -isystem /opt/rocm/include $(EXTRA
 
 # The library's objects, named once: the device ones (.hip) and the host ones
 # (.cpp), which the sanitizer build below compiles a second time.
-DEV_OBJS := rt_kernel.o rt_rays.o rt_aov.o rt_denoise.o rt_mis.o rt_lbvh.o rt_gsah.o rt_refit.o rt_mathcheck.o
+DEV_OBJS := rt_kernel.o rt_rays.o rt_aov.o rt_denoise.o rt_adaptive.o rt_mis.o rt_lbvh.o rt_gsah.o rt_refit.o rt_mathcheck.o
 HOST_OBJS := rt_api.o rt_api_host.o rt_scene.o rt_image.o
 OBJS := $(addprefix $(BLD)/,$(DEV_OBJS) $(HOST_OBJS))
-HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp
+HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp $(SRC)/rt_plan.hpp
 
 LIB ?= $(PKG)/librtpt.so
 # Hash of every source the library is built from (gpuraytracer_amd/srchash.py),
@@ -40,6 +40,7 @@ $(BLD)/%.o: $(SRC)/%.hip $(HDRS) $(SRC)/rt_trace.hpp | $(BLD)
 # the device-vs-host check of the shared scalar functions
 $(BLD)/rt_mathcheck.o $(BLD)/rt_image.o $(BLD)/rt_api_host.o: $(SRC)/rt_half.h $(SRC)/rt_mathcheck.hpp
 $(BLD)/rt_api_host.o: $(SRC)/rt_api_internal.hpp
+$(BLD)/rt_kernel.o: $(SRC)/rt_free.hpp $(SRC)/rt_counts.hpp
 
 $(BLD)/rt_api.o: $(SRC)/rt_api.cpp $(ALLSRC) | $(BLD)
 	$(HOSTCXX) $(HOSTFLAGS) -DRT_SRC_SHA='"$(SRC_SHA)"' -c $< -o $@

@@ -201,6 +201,27 @@ class DenoiseBuffers(ctypes.Structure):  # rt_denoise_buffers
 assert ctypes.sizeof(DenoiseParams) == 32 and ctypes.sizeof(DenoiseBuffers) == 40 and DenoiseBuffers.out.offset == 32
 
 
+RT_PLAN_RELATIVE = 0x800  # rt_plan_samples: weight by the relative luminance change
+
+
+class PlanParams(ctypes.Structure):  # rt_plan_params
+    _fields_ = [("budget", ctypes.c_uint64), ("count_min", ctypes.c_uint32), ("count_max", ctypes.c_uint32),
+                ("luminance_floor", ctypes.c_float), ("radius", ctypes.c_uint32), ("rows", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class PlanStats(ctypes.Structure):  # rt_plan_stats
+    _fields_ = [("weight_sum", ctypes.c_uint64), ("samples", ctypes.c_uint64),
+                ("count_max_seen", ctypes.c_uint32), ("at_cap", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert ctypes.sizeof(PlanParams) == 40 and ctypes.sizeof(PlanStats) == 32
+
+
 class MisParamsC(ctypes.Structure):  # rt_mis_params
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("camera_rays", "mis_samples", "row_start", "row_step", "row_count", "flags")]
@@ -232,6 +253,13 @@ SIGNATURES = {
     "rt_denoise_params_default": (None, [ctypes.POINTER(DenoiseParams)]),
     "rt_denoise": (ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers)]),
     "rt_denoise_async": (ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers), _P]),
+    "rt_render_counts": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P, _P]),
+    "rt_render_counts_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P, _P, _P]),
+    "rt_plan_params_default": (None, [ctypes.POINTER(PlanParams)]),
+    "rt_plan_samples": (ctypes.c_int, [_P, ctypes.POINTER(PlanParams), _P, _P, _P, ctypes.POINTER(PlanStats)]),
+    "rt_plan_samples_async": (ctypes.c_int, [_P, ctypes.POINTER(PlanParams), _P, _P, _P, _P, _P]),
+    "rt_plan_samples_host": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(PlanParams), _P, _P, _P,
+                                            ctypes.POINTER(PlanStats)]),
     "rt_debug_ray_domain": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(RayDomainInfo)]),
     "rt_last_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_destroy": (ctypes.c_int, [_P]),

@@ -128,6 +128,9 @@ struct rt_ctx {
     DevBuf d_rays, d_hits;         // staging for host rays and hits (rt_trace_rays)
     DevBuf d_aov[3];               // staging for host feature buffers (rt_render_aov)
     DevBuf d_den[6];               // rt_denoise: the (D, V) ping-pong, then staging for the four host inputs
+    DevBuf d_counts, d_totals;     // staging for host counts and totals (rt_render_counts, rt_plan_samples)
+    DevBuf d_plan_in[2];           // staging for the planner's two host images
+    DevBuf d_plan;                 // the planner's accumulators (rt::PlanStats)
     DevBuf d_seeds;
     bool seeds_ready = false;
     uint32_t seed_max = 0xFFFFFFFFu;  // max seed value (bounds the Halton index)
@@ -135,6 +138,9 @@ struct rt_ctx {
     bool sum_valid = false;
     uint32_t sum_row_start = 0, sum_row_step = 0, sum_row_count = 0;
     uint32_t sum_first = 0, sum_samples = 0;  // the sum holds samples [first, first + samples)
+    // rt_render_counts wrote the sum: pixel p holds the samples [first, first + its entry's .w), and
+    // sum_samples is an upper bound of those counts (it grows by the cap spp with each call)
+    bool sum_counts = false;
     bool timed = false;
     rt::LaunchInfo launch{};  // what the last launch that reports one launched (rt_last_launch)
     bool launched = false;
@@ -411,9 +417,18 @@ bool resolve_rows(const rt_ctx* c, uint32_t row_start, uint32_t row_step, uint32
     return *count <= avail;
 }
 
+// What rt_render_counts adds to a render: one count per pixel in, the totals out.
+struct CountsArgs {
+    const uint32_t* counts;
+    uint32_t* totals;  // or null
+};
+
+// rt_render / rt_render_async (ca == null) and rt_render_counts /
+// rt_render_counts_async: one launch of a path kernel over the context's tables.
 int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_device,
-                hipStream_t stream, bool sync) {
+                hipStream_t stream, bool sync, const CountsArgs* ca = nullptr) {
     if (!p) return fail(c, RT_ERR_INVALID_ARG, "params is null");
+    if (ca && !ca->counts) return fail(c, RT_ERR_INVALID_ARG, "rt_render_counts: counts is null");
     if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
     if (p->bounces > RT_MAX_BOUNCES)
         return fail(c, RT_ERR_INVALID_ARG,
@@ -427,16 +442,34 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     const bool sums = keep_sum || p->accumulate;
     if (want_out && !out) return fail(c, RT_ERR_INVALID_ARG, "out is null");
     if (p->accumulate) {
-        if (!c->sum_valid || c->sum_row_start != start || c->sum_row_step != step ||
-            c->sum_row_count != count ||
-            (uint64_t)c->sum_first + c->sum_samples != (uint64_t)p->sample_base)
-            return fail(c, RT_ERR_STATE,
-                        "accumulate: context sum does not end at sample_base for these rows "
-                        "(render with RT_KEEP_SUM first)");
+        const bool rows_same = c->sum_valid && c->sum_row_start == start && c->sum_row_step == step &&
+                               c->sum_row_count == count;
+        if (ca) {  // every pixel continues its own sequence, which started at sample_base
+            if (!rows_same || c->sum_first != p->sample_base)
+                return fail(c, RT_ERR_STATE,
+                            "rt_render_counts: accumulate: context sum does not start at sample_base for these rows "
+                            "(render with RT_KEEP_SUM first)");
+        } else {
+            if (rows_same && c->sum_counts)
+                return fail(c, RT_ERR_STATE,
+                            "accumulate: context sum holds per-pixel sample counts (rt_render_counts): "
+                            "continue it with rt_render_counts");
+            if (!rows_same || (uint64_t)c->sum_first + c->sum_samples != (uint64_t)p->sample_base)
+                return fail(c, RT_ERR_STATE,
+                            "accumulate: context sum does not end at sample_base for these rows "
+                            "(render with RT_KEEP_SUM first)");
+        }
     }
+    // a counts render: the upper bound of the totals (spp is the cap)
     const uint64_t total = (uint64_t)(p->accumulate ? c->sum_samples : 0u) + p->spp;
-    if (total == 0 || total > 0xFFFFFFFFull)
+    if (ca) {
+        if (total > (1ull << 24))
+            return fail(c, RT_ERR_INVALID_ARG,
+                        "rt_render_counts: the bound of the per-pixel totals (the caps spp of the calls into this "
+                        "sum) must stay <= 2^24");
+    } else if (total == 0 || total > 0xFFFFFFFFull) {
         return fail(c, RT_ERR_INVALID_ARG, "samples in the sum must be in [1, 2^32)");
+    }
 
     const size_t pixels = (size_t)count * (size_t)c->scene.cam.W;
     int st;
@@ -450,6 +483,20 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     if (want_out && !out_is_device) {
         if ((st = reserve(c, c->d_out, out_bytes, "hipMalloc(out staging)")) != RT_OK) return st;
         kout = c->d_out.as<void>();
+    }
+    const uint32_t* kcounts = ca ? ca->counts : nullptr;
+    uint32_t* ktotals = ca ? ca->totals : nullptr;
+    if (ca && !out_is_device) {  // host counts and totals through the context's staging buffers
+        if ((st = reserve(c, c->d_counts, pixels * sizeof(uint32_t), "hipMalloc(counts staging)")) != RT_OK) return st;
+        const hipError_t e = hipMemcpyAsync(c->d_counts.as<void>(), ca->counts, pixels * sizeof(uint32_t),
+                                            hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(counts)", e);
+        kcounts = c->d_counts.as<uint32_t>();
+        if (ca->totals) {
+            if ((st = reserve(c, c->d_totals, pixels * sizeof(uint32_t), "hipMalloc(totals staging)")) != RT_OK)
+                return st;
+            ktotals = c->d_totals.as<uint32_t>();
+        }
     }
 
     rt::KParams K;
@@ -487,11 +534,13 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     K.lanes = c->lanes;
     K.walk = c->walk;
     K.walk_leaf_den = c->walk_leaf_den;
-    K.max_index = halton_max_index(c, p->sample_base, p->spp);
+    // a counts render: pixel p's last index is sample_base + total_p - 1, and total_p <= total
+    K.max_index = halton_max_index(c, p->sample_base, ca ? (uint32_t)total : p->spp);
 
     if (keep_sum && !p->accumulate) c->sum_valid = false;  // being overwritten
-    if ((st = timed_launch(c, stream, "path_trace", &c->launch, [&](rt::LaunchInfo* info) {
-             return rt::launch_path_trace(K, p->bounces, c->scene_mem, stream, info);
+    if ((st = timed_launch(c, stream, ca ? "path_counts" : "path_trace", &c->launch, [&](rt::LaunchInfo* info) {
+             return ca ? rt::launch_path_counts(K, kcounts, ktotals, p->bounces, c->scene_mem, stream, info)
+                       : rt::launch_path_trace(K, p->bounces, c->scene_mem, stream, info);
          })) != RT_OK)
         return st;
     if (sums) {  // the kernel (re)wrote the running sums
@@ -501,7 +550,11 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
         c->sum_row_count = count;
         if (!p->accumulate) c->sum_first = p->sample_base;
         c->sum_samples = (uint32_t)total;
+        c->sum_counts = ca != nullptr;  // a uniform render never continues a counts sum
     }
+    if (ca && ca->totals && !out_is_device &&
+        (st = copy_down(c, ca->totals, ktotals, pixels * sizeof(uint32_t), stream, "hipMemcpyAsync(totals)")) != RT_OK)
+        return st;
     if (want_out && !out_is_device &&
         (st = copy_down(c, out, kout, out_bytes, stream, "hipMemcpyAsync(out)")) != RT_OK)
         return st;
@@ -874,6 +927,63 @@ int denoise_impl(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buffers
     return RT_OK;
 }
 
+// rt_plan_samples / rt_plan_samples_async: the planner's two kernels
+// (rt_adaptive.hip) on a tile of `rows` rows of the camera's width.  Host
+// images and counts go through the context's staging buffers on its own
+// stream; the statistics come from the context's accumulators.  `stats` is
+// host memory in the synchronous call, device memory in the asynchronous one.
+int plan_impl(rt_ctx* c, const rt_plan_params* p, const float* first, const float* all, uint32_t* counts,
+              rt_plan_stats* stats, bool dev, hipStream_t stream, bool sync) {
+    if (const char* why = plan_params_error(p, RT_OUT_DEVICE | RT_PLAN_RELATIVE))
+        return fail(c, RT_ERR_INVALID_ARG, std::string("rt_plan_samples: ") + why);
+    if (!first || !all || !counts) return fail(c, RT_ERR_INVALID_ARG, "rt_plan_samples: first, all or counts is null");
+    const uint32_t H = (uint32_t)c->scene.cam.H, rows = p->rows ? p->rows : H;
+    if (rows > H) return fail(c, RT_ERR_INVALID_ARG, "rt_plan_samples: rows exceeds the camera's height");
+    const size_t pixels = (size_t)rows * (size_t)c->scene.cam.W;
+    const size_t img_bytes = pixels * sizeof(float4), cnt_bytes = pixels * sizeof(uint32_t);
+    int st;
+    hipError_t e;
+    if ((st = reserve(c, c->d_plan, sizeof(rt::PlanStats), "hipMalloc(plan accumulators)")) != RT_OK) return st;
+    const void* kin[2] = {first, all};
+    uint32_t* kcounts = counts;
+    if (!dev) {
+        for (int k = 0; k < 2; ++k) {
+            if ((st = reserve(c, c->d_plan_in[k], img_bytes, "hipMalloc(plan staging)")) != RT_OK) return st;
+            if ((e = hipMemcpyAsync(c->d_plan_in[k].as<void>(), kin[k], img_bytes, hipMemcpyHostToDevice, stream)) !=
+                hipSuccess)
+                return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(plan inputs)", e);
+            kin[k] = c->d_plan_in[k].as<void>();
+        }
+        if ((st = reserve(c, c->d_counts, cnt_bytes, "hipMalloc(counts staging)")) != RT_OK) return st;
+        kcounts = c->d_counts.as<uint32_t>();
+    }
+    rt::PlanParams K{};
+    K.first = static_cast<const float4*>(kin[0]);
+    K.all = static_cast<const float4*>(kin[1]);
+    K.counts = kcounts;
+    K.acc = c->d_plan.as<rt::PlanStats>();
+    K.budget = p->budget;
+    K.count_min = p->count_min;
+    K.count_max = p->count_max;
+    K.luminance_floor = p->luminance_floor;
+    K.radius = p->radius;
+    K.W = c->scene.cam.W;
+    K.rows = (int32_t)rows;
+    K.flags = p->flags & RT_PLAN_RELATIVE;
+    if ((st = timed_launch(c, stream, "plan", &c->launch,
+                           [&](rt::LaunchInfo* info) { return rt::launch_plan(K, stream, info); })) != RT_OK)
+        return st;
+    if (!dev && (st = copy_down(c, counts, kcounts, cnt_bytes, stream, "hipMemcpyAsync(counts)")) != RT_OK) return st;
+    if (stats) {  // synchronous: host memory; asynchronous: device memory
+        e = hipMemcpyAsync(stats, K.acc, sizeof(rt_plan_stats), sync ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                           stream);
+        if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(plan stats)", e);
+    }
+    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "plan execution", e);
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1142,6 +1252,35 @@ int rt_denoise_async(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buf
     if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
     DeviceGuard g(c->device);
     return denoise_impl(c, p, b_dev, true, (hipStream_t)hip_stream, false);
+}
+
+int rt_render_counts(rt_ctx* c, const rt_render_params* p, const uint32_t* counts, void* out, uint32_t* totals) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    const CountsArgs ca{counts, totals};
+    return render_impl(c, p, out, p && (p->flags & RT_OUT_DEVICE), c->stream, true, &ca);
+}
+
+int rt_render_counts_async(rt_ctx* c, const rt_render_params* p, const uint32_t* counts_dev, void* out_dev,
+                           uint32_t* totals_dev, void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    const CountsArgs ca{counts_dev, totals_dev};
+    return render_impl(c, p, out_dev, true, (hipStream_t)hip_stream, false, &ca);
+}
+
+int rt_plan_samples(rt_ctx* c, const rt_plan_params* p, const float* first, const float* all, uint32_t* counts,
+                    rt_plan_stats* stats) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return plan_impl(c, p, first, all, counts, stats, p && (p->flags & RT_OUT_DEVICE), c->stream, true);
+}
+
+int rt_plan_samples_async(rt_ctx* c, const rt_plan_params* p, const float* first_dev, const float* all_dev,
+                          uint32_t* counts_dev, rt_plan_stats* stats_dev, void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return plan_impl(c, p, first_dev, all_dev, counts_dev, stats_dev, true, (hipStream_t)hip_stream, false);
 }
 
 int rt_last_kernel_ms(rt_ctx* c, float* ms) {

@@ -219,6 +219,58 @@ const char* rt_status_string(int s) {
     }
 }
 
+void rt_plan_params_default(rt_plan_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->count_max = rt::kPlanCountMax;
+    p->luminance_floor = 0.01f;
+    p->radius = 1;
+}
+
+// The planner of rt_adaptive.hip in plain C++: the same
+// per-pixel functions (rt_plan.hpp), the maximum and the sums in any order.
+int rt_plan_samples_host(int32_t width, const rt_plan_params* p, const float* first, const float* all,
+                         uint32_t* counts, rt_plan_stats* stats) {
+    if (const char* why = rtapi::plan_params_error(p, RT_PLAN_RELATIVE))
+        return rtapi::fail(nullptr, RT_ERR_INVALID_ARG, std::string("rt_plan_samples_host: ") + why);
+    if (!first || !all || !counts)
+        return rtapi::fail(nullptr, RT_ERR_INVALID_ARG, "rt_plan_samples_host: first, all or counts is null");
+    if (width < 1 || p->rows < 1 || p->rows > 0x7FFFFFFFu)
+        return rtapi::fail(nullptr, RT_ERR_INVALID_ARG, "rt_plan_samples_host: width and params->rows must be >= 1");
+    const int W = width, H = (int)p->rows, R = (int)p->radius;
+    const size_t n = (size_t)W * (size_t)H;
+    const bool relative = (p->flags & RT_PLAN_RELATIVE) != 0;
+    std::vector<uint32_t> q(n);
+    for (size_t k = 0; k < n; ++k) {
+        const float* f = first + 4 * k;
+        const float* a = all + 4 * k;
+        q[k] = rt::plan_weight(f[0], f[1], f[2], a[0], a[1], a[2], relative, p->luminance_floor);
+    }
+    uint64_t Q = 0;
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            uint32_t m = 0;
+            for (int j = std::max(0, y - R); j <= std::min(H - 1, y + R); ++j)
+                for (int i = std::max(0, x - R); i <= std::min(W - 1, x + R); ++i)
+                    m = std::max(m, q[(size_t)j * (size_t)W + (size_t)i]);
+            counts[(size_t)y * (size_t)W + (size_t)x] = m;
+            Q += m;
+        }
+    rt_plan_stats s{};
+    s.weight_sum = Q;
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t share = rt::plan_share(p->budget, counts[k], Q, p->count_min);
+        const bool capped = share > (uint64_t)p->count_max;
+        const uint32_t c = capped ? p->count_max : (uint32_t)share;
+        counts[k] = c;
+        s.samples += c;
+        s.at_cap += capped ? 1u : 0u;
+        s.count_max_seen = std::max(s.count_max_seen, c);
+    }
+    if (stats) *stats = s;
+    return RT_OK;
+}
+
 void rt_denoise_params_default(rt_denoise_params* p) {
     if (!p) return;
     memset(p, 0, sizeof(*p));

@@ -9,6 +9,7 @@
 
 #include "../../include/rtpt.h"
 #include "rt_kernel.hpp"
+#include "rt_plan.hpp"
 #include "rt_scene.hpp"
 
 namespace rtapi {
@@ -93,6 +94,24 @@ inline TileLayout tile_layout(uint32_t W, uint32_t H, uint32_t N, uint32_t rank,
     L.row_bytes = (size_t)W * pixel_bytes(flags);
     L.tile_bytes = (size_t)L.rows_max * L.row_bytes;
     return L;
+}
+
+// rt_plan_params (rt_plan_samples and rt_plan_samples_host): null when every
+// field is in its range, else what is wrong.  `flags_ok`: the flag bits the
+// entry point accepts.
+inline const char* plan_params_error(const rt_plan_params* p, uint32_t flags_ok) {
+    static_assert(sizeof(rt_plan_params) == 40 && sizeof(rt_plan_stats) == 32 && sizeof(rt::PlanStats) == 32,
+                  "rt_plan_params / rt_plan_stats layout");
+    if (!p) return "params is null";
+    if (p->flags & ~flags_ok) return "unknown flag bits";
+    if (p->reserved[0] || p->reserved[1]) return "reserved must be 0";
+    if (p->count_max > rt::kPlanCountMax) return "count_max must be <= 2^24";
+    if (p->count_min > p->count_max) return "count_min must be <= count_max";
+    if (p->budget >= rt::kPlanBudgetEnd) return "budget must be < 2^38";
+    if (p->radius > rt::kPlanRadiusMax) return "radius must be in [0, 2]";
+    if ((p->flags & RT_PLAN_RELATIVE) && !(p->luminance_floor > 0.0f))
+        return "luminance_floor must be > 0 with RT_PLAN_RELATIVE";
+    return nullptr;
 }
 
 // halton(i, d) of the SwiftPM kernel (Sources/gpuRaytracer/shaders.metal:32-47),

@@ -44,7 +44,7 @@ constexpr uint32_t kThreads = kDenoiseTile * kDenoiseTile;
 constexpr float kAlbedoFloor = 0x1p-10f;
 constexpr float kNoCoverage = -1.0f;  // V of a pixel without coverage (V >= 0 otherwise)
 
-__device__ __forceinline__ float lum(float r, float g, float b) { return fmaf(b, 0.0722f, fmaf(g, 0.7152f, r * 0.2126f)); }
+// lum: rt_math.h (shared with the sample planner)
 __device__ __forceinline__ bool covered(float v) { return v >= 0.0f; }
 
 // The texels around one pixel in global memory; outside the frame a texel reads

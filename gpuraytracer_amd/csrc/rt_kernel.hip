@@ -1233,6 +1233,8 @@ hipError_t launch_path_trace(const KParams& P, uint32_t bounces, SceneMem mem,
     return e;
 }
 
+// the render with per-pixel sample counts: after every kernel and launcher above
+#include "rt_counts.hpp"
 
 hipError_t lds_check_result(uint32_t* end) {
     *end = 0;

@@ -232,6 +232,15 @@ enum class SceneMem { kAuto = 0, kLdsSingle = 1, kSmem = 2, kPairSorted = 3, kPa
 hipError_t launch_path_trace(const KParams& P, uint32_t bounces, SceneMem mem, hipStream_t stream,
                              LaunchInfo* info);
 KernelChoice choose_kernel(const SceneTables& t, bool sph_compact, uint32_t bounces, SceneMem mem, uint32_t walk);
+// The render with one sample count per pixel (rt_counts.hpp; include/rtpt.h
+// rt_render_counts): pixel p draws min(counts[p], P.spp) samples after the
+// P.sum[p].w samples its sum holds (P.accumulate), `totals` (or null) receives
+// the new total.  counts / totals: row_count * W words of device memory in the
+// layout of P.out.  P.samples_total and P.lanes are not read; P.max_index
+// bounds seed + sample_base + every total.  The layout is ray_query_layout of
+// the context's.
+hipError_t launch_path_counts(const KParams& P, const uint32_t* counts, uint32_t* totals, uint32_t bounces,
+                              SceneMem mem, hipStream_t stream, LaunchInfo* info);
 hipError_t read_debug_stats(unsigned long long* out, int n);  // RT_STATS builds only
 // -DRT_LDS_CHECK builds: the largest staging end a kernel found past its
 // dispatch's dynamic LDS since the last call (0: none; always 0 otherwise).
@@ -348,6 +357,29 @@ struct DenoiseParams {
 };
 // prepare, variance pre-filter, `iterations` a-trous launches; *info: the last.
 hipError_t launch_denoise(const DenoiseParams& P, hipStream_t stream, LaunchInfo* info);
+
+// ---- sample planner (rt_adaptive.hip; include/rtpt.h rt_plan_samples) -------
+constexpr uint32_t kPlanTile = 16;  // pixels on a side of a workgroup's tile
+// rt_plan_stats, and the planner's accumulators on the device
+struct PlanStats {
+    unsigned long long weight_sum, samples;
+    uint32_t count_max_seen, at_cap;
+    uint32_t reserved[2];
+};
+struct PlanParams {
+    const float4* first;   // rows * W pixels each, device memory
+    const float4* all;
+    uint32_t* counts;      // rows * W words: the dilated weights, then the counts
+    PlanStats* acc;        // zeroed by the launcher, complete when the stream has run the launches
+    unsigned long long budget;
+    uint32_t count_min, count_max;
+    float luminance_floor;
+    uint32_t radius;       // 0..2
+    int32_t W, rows;
+    uint32_t flags;        // kPlanRelative (rt_plan.hpp)
+};
+// the memset of P.acc, plan_weights_kernel, plan_counts_kernel; *info: the last
+hipError_t launch_plan(const PlanParams& P, hipStream_t stream, LaunchInfo* info);
 
 hipError_t launch_mis(const MisParams& P, SceneMem mem, hipStream_t stream);
 size_t mis_lds_bytes(uint32_t n_tri, uint32_t n_pairs);

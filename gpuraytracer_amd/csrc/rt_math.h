@@ -91,6 +91,8 @@ RT_HD f3 normalize(f3 a) { return a * rcp_cr(sqrt_cr(dot(a, a))); }
 RT_HD float length_ieee(f3 a) { return sqrtf(dot(a, a)); }
 RT_HD f3 normalize_ieee(f3 a) { return a * (1.0f / sqrtf(dot(a, a))); }
 RT_HD float saturate(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+// Rec. 709 luminance of the denoiser and the sample planner (§3.27)
+RT_HD float lum(float r, float g, float b) { return fmaf(b, 0.0722f, fmaf(g, 0.7152f, r * 0.2126f)); }
 
 // Halton bases: `constant unsigned int primes[]` (RTrace/sampling.metal:97-104).
 #define RT_PRIMES_INIT {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, \

@@ -21,7 +21,7 @@ import numpy as np
 from ._native import (MATH_FNS, RT_MATH_DEVICE, RT_MATH_HOST, RT_MATH_VALUES_MAX, LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, RT_UPDATE_REBUILD, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
-                      RenderParamsC,
+                      PlanParams, PlanStats, RT_PLAN_RELATIVE, RenderParamsC,
                       RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, UpdateStats, float3,
                       lib)
 
@@ -124,6 +124,40 @@ def place_tiles_host(gathered: np.ndarray, width: int, height: int, world: int) 
     _check(lib.rt_place_tiles_host(g.ctypes.data_as(ctypes.c_void_p), width, height, world,
                                    _pixel_flags(fp16, rgba8), frame.ctypes.data_as(ctypes.c_void_p)))
     return frame
+
+
+def _plan_params(budget, count_min, count_max, radius, relative, luminance_floor) -> PlanParams:
+    p = PlanParams()
+    lib.rt_plan_params_default(ctypes.byref(p))
+    p.budget, p.count_min, p.count_max, p.radius = budget, count_min, count_max, radius
+    p.luminance_floor = luminance_floor
+    p.flags = RT_PLAN_RELATIVE if relative else 0
+    return p
+
+
+def _plan_images(first, all, width=None):
+    f = np.ascontiguousarray(first, dtype=np.float32)
+    a = np.ascontiguousarray(all, dtype=np.float32)
+    if f.ndim != 3 or f.shape[2] != 4 or a.shape != f.shape or (width is not None and f.shape[1] != width):
+        raise ValueError("first and all must be (rows, W, 4) float32 images of one shape")
+    return f, a
+
+
+def plan_samples_host(first, all, budget: int, count_min: int = 0, count_max: int = 1 << 24, radius: int = 1,
+                      relative: bool = False, luminance_floor: float = 0.01, return_stats: bool = False):
+    """rt_plan_samples_host: the sample planner of ``Renderer.plan_samples`` in
+    plain C++ on the host (no device, no scene), bit for bit the same counts.
+    ``first`` / ``all``: (rows, W, 4) float32.  Returns the (rows, W) uint32
+    counts, with ``return_stats`` also the rt_plan_stats as a dict."""
+    f, a = _plan_images(first, all)
+    p = _plan_params(budget, count_min, count_max, radius, relative, luminance_floor)
+    p.rows = f.shape[0]
+    counts = np.empty(f.shape[:2], np.uint32)
+    s = PlanStats()
+    _check(lib.rt_plan_samples_host(f.shape[1], ctypes.byref(p), f.ctypes.data_as(ctypes.c_void_p),
+                                    a.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p),
+                                    ctypes.byref(s)))
+    return (counts, s.as_dict()) if return_stats else counts
 
 
 def _tri_bvh_dump(call, n: int, nodes_cap: int) -> dict:
@@ -720,6 +754,170 @@ class Renderer:
         if hasattr(s, "synchronize"):
             s.synchronize()
         return (img, inputs) if return_inputs else img
+
+    def _stream_handle(self, stream):
+        """(torch stream to wait for or None, raw hipStream_t) for a device call."""
+        import torch  # plumbing only: the caller's stream
+        cur = torch.cuda.current_stream(self.device) if stream is None else None
+        return cur, (cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream))
+
+    def render_counts(self, params: RenderParams, counts, out=None, totals=None, stream=None):
+        """rt_render_counts: :meth:`render` with one sample
+        count per pixel.  ``counts`` is (rows, W) uint32 in the layout of the
+        image; ``params.spp`` is a cap, pixel p draws ``min(counts[p], spp)``
+        samples after the ``k_p`` its running sum holds (``accumulate``), and
+        equals the same pixel of ``render`` at ``spp = total_p`` from
+        ``sample_base``, bit for bit.  ``options.lanes_per_pixel`` is ignored.
+
+        A numpy ``counts`` takes the host path and blocks; a contiguous 4-byte
+        integer torch tensor on the context's device takes the device path,
+        enqueued on ``stream`` without a host sync (default: torch's current
+        stream, then waited for), with ``out`` a device tensor (allocated when
+        None).  ``totals``: True, or an array / tensor like ``counts``, to
+        receive the per-pixel totals.  Returns the image, or ``(image,
+        totals)`` when totals were asked for."""
+        p = params
+        rows, W = p.rows(self.scene.height), self.scene.width
+        if isinstance(counts, np.ndarray):
+            cn = np.ascontiguousarray(counts, dtype=np.uint32)
+            if cn.shape != (rows, W):
+                raise ValueError(f"counts must have shape {(rows, W)}")
+            dt = np.uint8 if p.rgba8 else np.uint16 if p.fp16 else np.float32
+            img = np.empty((rows, W, 4), dtype=dt) if out is None else out
+            if not isinstance(img, np.ndarray) or img.dtype != dt or img.shape != (rows, W, 4) or not img.flags.c_contiguous:
+                raise ValueError(f"out must be a contiguous {(rows, W, 4)} {np.dtype(dt)} array")
+            tot = np.empty((rows, W), np.uint32) if totals is True else totals
+            if tot is not None and (not isinstance(tot, np.ndarray) or tot.dtype != np.uint32 or tot.shape != (rows, W)
+                                    or not tot.flags.c_contiguous):
+                raise ValueError(f"totals must be a contiguous {(rows, W)} uint32 array")
+            _check(lib.rt_render_counts(self._ctx, ctypes.byref(p.c()), cn.ctypes.data_as(ctypes.c_void_p),
+                                        img.ctypes.data_as(ctypes.c_void_p),
+                                        None if tot is None else tot.ctypes.data_as(ctypes.c_void_p)), self._ctx)
+            return img if tot is None else (img, tot)
+        import torch  # plumbing only: device memory and the caller's stream
+
+        def word_tensor(t, name):
+            if (not isinstance(t, torch.Tensor) or t.element_size() != 4 or t.is_floating_point()
+                    or tuple(t.shape) != (rows, W) or not t.is_contiguous() or not t.is_cuda
+                    or t.device.index != self.device):
+                raise ValueError(f"{name} must be a contiguous {(rows, W)} 4-byte integer tensor on the context's device")
+        word_tensor(counts, "counts")
+        dt = torch.uint8 if p.rgba8 else torch.float16 if p.fp16 else torch.float32
+        img = torch.empty((rows, W, 4), dtype=dt, device=counts.device) if out is None else out
+        tot = torch.empty((rows, W), dtype=torch.int32, device=counts.device) if totals is True else totals
+        if tot is not None:
+            word_tensor(tot, "totals")
+        cur, handle = self._stream_handle(stream)
+        ptr = img if isinstance(img, int) else img.data_ptr()
+        _check(lib.rt_render_counts_async(self._ctx, ctypes.byref(p.c(RT_OUT_DEVICE)), ctypes.c_void_p(counts.data_ptr()),
+                                          ctypes.c_void_p(ptr), ctypes.c_void_p(None if tot is None else tot.data_ptr()),
+                                          ctypes.c_void_p(handle)), self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        return img if tot is None else (img, tot)
+
+    def plan_samples(self, first, all, budget: int, count_min: int = 0, count_max: int = 1 << 24, radius: int = 1,
+                     relative: bool = False, luminance_floor: float = 0.01, counts=None, return_stats: bool = False,
+                     stream=None):
+        """rt_plan_samples: sample counts from a pilot
+        render.  ``first`` / ``all``: (rows, W, 4) float32 images of the
+        pilot's first half and of all its samples.  ``budget`` samples are
+        handed out over the tile beyond ``count_min`` each, in proportion to
+        the ``radius``-dilated luminance change between the two images
+        (``relative``: divided by ``lum(all) + luminance_floor``), each count
+        capped at ``count_max``.  numpy arrays take the host path; contiguous
+        torch tensors on the context's device the device path on ``stream``
+        (default: torch's current stream, then waited for).  Returns the
+        (rows, W) counts (uint32 array / int32 tensor), with ``return_stats``
+        also the rt_plan_stats as a dict (the device path then waits)."""
+        p = _plan_params(budget, count_min, count_max, radius, relative, luminance_floor)
+        W = self.scene.width
+        s = PlanStats()
+        if isinstance(first, np.ndarray):
+            f, a = _plan_images(first, all, W)
+            p.rows = f.shape[0]
+            cn = np.empty(f.shape[:2], np.uint32) if counts is None else counts
+            if not isinstance(cn, np.ndarray) or cn.dtype != np.uint32 or cn.shape != f.shape[:2] or not cn.flags.c_contiguous:
+                raise ValueError(f"counts must be a contiguous {f.shape[:2]} uint32 array")
+            _check(lib.rt_plan_samples(self._ctx, ctypes.byref(p), f.ctypes.data_as(ctypes.c_void_p),
+                                       a.ctypes.data_as(ctypes.c_void_p), cn.ctypes.data_as(ctypes.c_void_p),
+                                       ctypes.byref(s)), self._ctx)
+            return (cn, s.as_dict()) if return_stats else cn
+        import torch  # plumbing only: device memory and the caller's stream
+        for k, t in (("first", first), ("all", all)):
+            if (not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (W, 4) or t.shape != first.shape
+                    or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda
+                    or t.device.index != self.device):
+                raise ValueError(f"{k} must be a contiguous (rows, {W}, 4) float32 tensor on the context's device")
+        rows = first.shape[0]
+        p.rows = rows
+        p.flags |= RT_OUT_DEVICE
+        cn = torch.empty((rows, W), dtype=torch.int32, device=first.device) if counts is None else counts
+        if (not isinstance(cn, torch.Tensor) or cn.element_size() != 4 or cn.is_floating_point()
+                or tuple(cn.shape) != (rows, W) or not cn.is_contiguous() or cn.device != first.device):
+            raise ValueError(f"counts must be a contiguous {(rows, W)} 4-byte integer tensor on the images' device")
+        st = torch.empty(ctypes.sizeof(PlanStats), dtype=torch.uint8, device=first.device) if return_stats else None
+        cur, handle = self._stream_handle(stream)
+        _check(lib.rt_plan_samples_async(self._ctx, ctypes.byref(p), ctypes.c_void_p(first.data_ptr()),
+                                         ctypes.c_void_p(all.data_ptr()), ctypes.c_void_p(cn.data_ptr()),
+                                         ctypes.c_void_p(None if st is None else st.data_ptr()),
+                                         ctypes.c_void_p(handle)), self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        if not return_stats:
+            return cn
+        if cur is None:
+            torch.cuda.synchronize(first.device) if not hasattr(stream, "synchronize") else stream.synchronize()
+        return cn, PlanStats.from_buffer_copy(st.cpu().numpy().tobytes()).as_dict()
+
+    def render_adaptive(self, params: RenderParams, pilot_spp: int, mean_spp: int, radius: int = 1,
+                        relative: bool = False, luminance_floor: float = 0.01, count_min: int = 0,
+                        return_totals: bool = False, return_stats: bool = False, device: bool = False, stream=None):
+        """An adaptively sampled render of ``mean_spp``
+        samples per pixel on average, at most ``params.spp`` (the cap) at any
+        pixel: a pilot of ``pilot_spp`` samples in two halves (``keep_sum``,
+        then ``accumulate``, so no sample is rendered twice), the plan with
+        ``budget = (mean_spp - pilot_spp) * pixels`` from the two pilot images,
+        and one accumulating counts render.  Equal to those four calls made by
+        hand.  Float32 images of ``params``' rows; the running sum is kept.
+
+        Host path by default ((rows, W, 4) float32 array); ``device``: torch
+        tensors on the context's device, everything enqueued on ``stream``
+        (default: torch's current stream), then waited for.  Returns the
+        image, followed by the totals (``return_totals``) and the plan's
+        statistics (``return_stats``) when asked for."""
+        p = params
+        if pilot_spp < 2 or pilot_spp % 2:
+            raise ValueError("render_adaptive needs an even pilot_spp >= 2 (two halves)")
+        if mean_spp < pilot_spp or p.spp < pilot_spp:
+            raise ValueError("render_adaptive needs pilot_spp <= mean_spp and pilot_spp <= params.spp (the cap)")
+        if p.accumulate or p.fp16 or p.rgba8:
+            raise ValueError("render_adaptive renders float32 frames from a new sum (no accumulate, fp16, rgba8)")
+        rows, W, h = p.rows(self.scene.height), self.scene.width, pilot_spp // 2
+        part = dict(bounces=p.bounces, row_start=p.row_start, row_step=p.row_step, row_count=p.row_count)
+        first_p = RenderParams(spp=h, sample_base=p.sample_base, keep_sum=True, **part)
+        all_p = RenderParams(spp=h, sample_base=p.sample_base + h, accumulate=True, keep_sum=True, **part)
+        rest_p = RenderParams(spp=p.spp - pilot_spp, sample_base=p.sample_base, accumulate=True, keep_sum=True, **part)
+        plan = dict(budget=(mean_spp - pilot_spp) * rows * W, count_min=count_min, count_max=max(p.spp - pilot_spp, count_min),
+                    radius=radius, relative=relative, luminance_floor=luminance_floor, return_stats=True)
+        if not device:
+            first, both = self.render(first_p), self.render(all_p)
+            counts, stats = self.plan_samples(first, both, **plan)
+            img, totals = self.render_counts(rest_p, counts, totals=True)
+        else:
+            import torch  # plumbing only: device memory and the caller's stream
+            dev = torch.device("cuda", self.device)
+            s = torch.cuda.current_stream(dev) if stream is None else stream
+            first = torch.empty((rows, W, 4), dtype=torch.float32, device=dev)
+            both = torch.empty_like(first)
+            self.render(first_p, out=first, stream=s)
+            self.render(all_p, out=both, stream=s)
+            counts, stats = self.plan_samples(first, both, stream=s, **plan)
+            img, totals = self.render_counts(rest_p, counts, out=first, totals=True, stream=s)
+            if hasattr(s, "synchronize"):
+                s.synchronize()
+        res = (img,) + ((totals,) if return_totals else ()) + ((stats,) if return_stats else ())
+        return res if len(res) > 1 else img
 
     def render_progressive(self, params: RenderParams, batch_spp: int, out, stream=None,
                            gather: bool = False):

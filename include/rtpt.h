@@ -439,6 +439,116 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_bu
 int rt_denoise_async(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_buffers* buffers_dev,
                      void* hip_stream);
 
+/* ---- adaptive sampling: per-pixel sample counts and a sample planner --------
+ * rt_render_counts is rt_render with one sample count per pixel; rt_plan_samples
+ * makes such counts from a pilot render.  These entry points
+ * were added without a change of RTPT_ABI_VERSION (nothing else changed): a
+ * caller that may meet an older library detects the feature by the presence of
+ * the symbol rt_render_counts (dlsym).
+ *
+ * rt_render_counts: `counts` and `totals` (optional) hold row_count * W words
+ * in the layout of `out` (tile row j, column x): host memory (the context's
+ * staging buffers carry them), or all device memory with RT_OUT_DEVICE.
+ * params->spp is a cap: pixel p draws c_p = min(counts[p], spp) samples.
+ *   accumulate = 0: pixel p renders the samples [sample_base, sample_base + c_p);
+ *                   its total is c_p.
+ *   accumulate = 1: the context's running sum must hold, for these rows, a
+ *                   sequence that started at sample_base (RT_ERR_STATE
+ *                   otherwise).  Pixel p already holds k_p samples (the fourth
+ *                   word of its sum entry), renders
+ *                   [sample_base + k_p, sample_base + k_p + c_p), and its total
+ *                   is k_p + c_p.
+ * The pixel is (sum / (float)total, 1) in the format the flags ask for, colour
+ * +0 where the total is 0; with RT_KEEP_SUM its sum entry becomes
+ * (sum, (float)total); `totals` receives the total.  So pixel p equals the same
+ * pixel of rt_render with spp = total_p from sample_base, bit for bit, whatever
+ * its neighbours' counts, and uniform counts reproduce rt_render.
+ *
+ * The context keeps an upper bound of the totals, which grows by spp with each
+ * accumulating call and must stay <= 2^24 (RT_ERR_INVALID_ARG above: the sum's
+ * count stays an exact float).  After a counts call the sum holds per-pixel
+ * counts: rt_render with accumulate = 1 then returns RT_ERR_STATE; a counts call
+ * may continue a uniform sum; a non-accumulating RT_KEEP_SUM render starts a
+ * uniform sum again; rt_update_scene drops the sum.  RT_OUT_NONE, the
+ * RT_OUT_FP16 / RT_OUT_RGBA8 exclusivity, the row partition and the seeds
+ * behave as for rt_render.  An all-zero map is RT_OK.
+ *
+ * The kernel is rt::path_counts_kernel<B, layout, spheres, small, L>
+ * (rt_last_launch): L = 16 lanes per pixel for fixed-digit Halton indices, one
+ * lane per pixel otherwise; rt_create_options.lanes_per_pixel is ignored, and
+ * a context of RT_WALK_FREE, RT_WALK_SORTED or RT_LAYOUT_SORTED renders counts
+ * through its lockstep form. */
+int rt_render_counts(rt_ctx* ctx, const rt_render_params* params, const uint32_t* counts, void* out,
+                     uint32_t* totals);
+
+/* Asynchronous variant: counts, out and totals are device memory, the kernel is
+ * enqueued on `hip_stream` (a hipStream_t, NULL = the null stream).  No host
+ * sync. */
+int rt_render_counts_async(rt_ctx* ctx, const rt_render_params* params, const uint32_t* counts_dev, void* out_dev,
+                           uint32_t* totals_dev, void* hip_stream);
+
+/* rt_plan_samples: sample counts from a pilot render.  `first` is the rgba32F
+ * image of the pilot's first h samples, `all` the image of all 2h: the outputs
+ * of the two calls that build the running sum (h samples with RT_KEEP_SUM, then
+ * h more with accumulate = 1), so no sample is rendered twice.  Both are
+ * rows * W pixels; the neighbourhood is taken within that tile (the rows of an
+ * interleaved share are treated as adjacent).  Per pixel, in fp32 under the
+ * contract of DESIGN.md §3 up to q and in integers from there:
+ *   el = |lum(all) - lum(first)|            lum: the denoiser's (§3.23)
+ *   r  = el, or el / (lum(all) + luminance_floor) with RT_PLAN_RELATIVE
+ *   r  = (r >= 0) ? r : 0                   NaN gives 0
+ *   q  = 1 + (uint32)min(r * 65536.0f, 16777216.0f)
+ *   m  = max of q over the in-tile (2 radius + 1)^2 neighbourhood
+ *   Q  = sum of m over the tile (64 bit)
+ *   counts = min(count_max, count_min + (budget * m) / Q)    in 64-bit integers
+ * Samples lost to the cap are not redistributed:
+ * sum(counts) <= pixels * count_min + budget.  Any 32 bytes per pixel give a
+ * defined answer and no address depends on data; the device, the host function
+ * and tests/adaptive_ref.py agree bit for bit. */
+#define RT_PLAN_RELATIVE 0x800u
+typedef struct rt_plan_params {
+    uint64_t budget;         /* samples to hand out over the tile beyond count_min each, < 2^38 */
+    uint32_t count_min, count_max;   /* count_min <= count_max <= 2^24                          */
+    float luminance_floor;   /* RT_PLAN_RELATIVE: > 0                                           */
+    uint32_t radius;         /* 0..2: dilation                                                  */
+    uint32_t rows;           /* rows of the tile, 0 = the camera's H                            */
+    uint32_t flags;          /* RT_OUT_DEVICE, RT_PLAN_RELATIVE                                 */
+    uint32_t reserved[2];    /* must be 0                                                       */
+} rt_plan_params; /* 40 B */
+
+typedef struct rt_plan_stats {
+    uint64_t weight_sum;     /* Q                                                               */
+    uint64_t samples;        /* sum of counts                                                   */
+    uint32_t count_max_seen; /* the largest count                                               */
+    uint32_t at_cap;         /* pixels whose share was cut by count_max                         */
+    uint32_t reserved[2];    /* 0                                                               */
+} rt_plan_stats; /* 32 B */
+
+/* budget 0, count_min 0, count_max 2^24, luminance_floor 0.01f, radius 1,
+ * rows 0, flags 0 (absolute), reserved {0, 0}. */
+void rt_plan_params_default(rt_plan_params* params);
+
+/* Plan and block until done.  first / all / counts (and stats, optional) are
+ * host memory, or first / all / counts device memory with RT_OUT_DEVICE (stats
+ * stays host memory).  The tile is `rows` rows (<= H) of the camera's width.
+ * The context owns the planner's scratch (its staging buffers and 32 B of
+ * accumulators), grown on first use and freed by rt_destroy; calls on one
+ * context must be ordered.  RT_ERR_INVALID_ARG with a message: a NULL pointer,
+ * count_min > count_max, count_max > 2^24, budget >= 2^38, radius > 2, a floor
+ * not > 0 with RT_PLAN_RELATIVE, rows > H, nonzero reserved, unknown flag bits. */
+int rt_plan_samples(rt_ctx* ctx, const rt_plan_params* params, const float* first, const float* all,
+                    uint32_t* counts, rt_plan_stats* stats);
+
+/* Asynchronous variant: first, all, counts and stats_dev (optional) are device
+ * memory; enqueued on `hip_stream`.  No host sync. */
+int rt_plan_samples_async(rt_ctx* ctx, const rt_plan_params* params, const float* first_dev, const float* all_dev,
+                          uint32_t* counts_dev, rt_plan_stats* stats_dev, void* hip_stream);
+
+/* The same plan in plain C++ on the host (no device, no context): a tile of
+ * params->rows (>= 1) rows of `width` pixels.  RT_OUT_DEVICE is not accepted. */
+int rt_plan_samples_host(int32_t width, const rt_plan_params* params, const float* first, const float* all,
+                         uint32_t* counts, rt_plan_stats* stats);
+
 /* The exactness domain of a scene (host-only, no device): a ray is in it when
  * all eight floats are finite, max |origin component| <= origin_max,
  * dir_len2_min <= dot(dir, dir) <= dir_len2_max and

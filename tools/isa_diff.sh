@@ -9,9 +9,12 @@
 # derives the compilation-unit id (the __hip_cuid_* symbol) from the source
 # path, the only path-dependent text in the assembly.  One line per
 # file: identical (with the sha256 of the .s), or the symbol that holds the
-# first difference; a file the revision lacks is reported as new.  Exit
-# status 1 on any difference.  rt_kernel.hip takes
-# minutes per compile; the ten compiles run ISA_JOBS (default 4) at a time.
+# first difference; a file the revision lacks is reported as new.  A file that
+# differs as a whole is compared function by function (tools/isa_funcs.py): when
+# every function of <git-rev> is there unchanged, functions were only added,
+# which is reported and is no difference.  Exit status 1 on any difference.
+# rt_kernel.hip takes minutes per compile; the compiles run ISA_JOBS (default
+# 4) at a time.
 set -eu
 [ $# -eq 1 ] || { echo "usage: $0 <git-rev>" >&2; exit 2; }
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -19,7 +22,7 @@ T=$(mktemp -d)
 trap 'git -C "$R" worktree remove --force "$T/rev" >/dev/null 2>&1 || true; rm -rf "$T"' EXIT
 git -C "$R" worktree add --detach "$T/rev" "$1" >/dev/null
 CC=$(make -s -C "$R" --eval 'isa-cc: ; @echo $(HIPCC) $(HIPFLAGS)' isa-cc)
-FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_refit rt_aov rt_denoise rt_mathcheck"
+FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_refit rt_aov rt_denoise rt_adaptive rt_mathcheck"
 mkdir -p "$T/new" "$T/old"
 export T CC
 for f in $FILES; do
@@ -34,11 +37,16 @@ for f in $FILES; do
         echo "$f.hip: new (sha256 $(sha256sum <"$T/new/$f.s" | cut -d' ' -f1))"
     elif cmp -s "$T/new/$f.s" "$T/old/$f.s"; then
         echo "$f.hip: identical (sha256 $(sha256sum <"$T/new/$f.s" | cut -d' ' -f1))"
+    elif funcs=$(python3 "$R/tools/isa_funcs.py" "$T/new/$f.s" "$T/old/$f.s"); then
+        # the file as a whole differs, but every function <git-rev> has is identical: functions were added
+        echo "$f.hip: existing functions identical, new ones added"
+        echo "$funcs"
     else
         # the last symbol label (name: in column 0, not a local .L label) at or before the first differing line
         line=$(cmp "$T/new/$f.s" "$T/old/$f.s" | sed -n 's/.* line \([0-9]*\)$/\1/p')
         sym=$(head -n "${line:-1}" "$T/new/$f.s" | grep -E '^[A-Za-z_$][A-Za-z0-9_.$]*:' | tail -1)
         echo "$f.hip: DIFFERS at line ${line:-?} of the assembly, in ${sym%:}"
+        echo "$funcs"
         rc=1
     fi
 done
