@@ -40,7 +40,7 @@ $(BLD)/%.o: $(SRC)/%.hip $(HDRS) $(SRC)/rt_trace.hpp | $(BLD)
 # the device-vs-host check of the shared scalar functions
 $(BLD)/rt_mathcheck.o $(BLD)/rt_image.o $(BLD)/rt_api_host.o: $(SRC)/rt_half.h $(SRC)/rt_mathcheck.hpp
 $(BLD)/rt_api_host.o: $(SRC)/rt_api_internal.hpp
-$(BLD)/rt_kernel.o: $(SRC)/rt_free.hpp $(SRC)/rt_counts.hpp
+$(BLD)/rt_kernel.o: $(SRC)/rt_free.hpp $(SRC)/rt_counts.hpp $(SRC)/rt_paths.hpp
 
 $(BLD)/rt_api.o: $(SRC)/rt_api.cpp $(ALLSRC) | $(BLD)
 	$(HOSTCXX) $(HOSTFLAGS) -DRT_SRC_SHA='"$(SRC_SHA)"' -c $< -o $@

@@ -14,7 +14,8 @@ reference's Swift host API, used by the tests and ``bench.py``:
   (albedo, normal, depth, coverage, primitive id) of the beauty samples;
   ``denoise`` / ``render_denoised`` filter a low-spp render with them;
   ``render_counts`` renders one sample count per pixel, ``plan_samples`` makes
-  such counts from a pilot render and ``render_adaptive`` runs the pipeline.
+  such counts from a pilot render and ``render_adaptive`` runs the pipeline;
+  ``trace_paths`` path-traces radiance along the caller's own rays.
 
 There is no CPU fallback: importing fails loudly when ``librtpt.so`` has not
 been built (``make`` or ``__graft_entry__.build()``), and rendering fails
@@ -23,7 +24,7 @@ loudly without a HIP device.
 from __future__ import annotations
 
 from ._native import (ABI_VERSION, RT_AOV_CENTER, RT_RAYS_CHUNK, AovBuffers, AovParams, CameraGPU, DenoiseBuffers,
-                      DenoiseParams, MaterialGPU, PlanParams, PlanStats, RT_PLAN_RELATIVE, RtError, SphereGPU, SquareLightGPU, float3, lib, library_path)
+                      DenoiseParams, MaterialGPU, PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, RtError, SphereGPU, SquareLightGPU, float3, lib, library_path)
 from .host import (DEFAULT_SEED_KEY, MisParams, Options, RenderParams, Renderer, Scene, comm_unique_id,
                    math_sums, math_values, place_tiles_host, plan_samples_host, seed_splitmix, tile_layout, tonemap_rgba8)
 
@@ -33,5 +34,5 @@ __all__ = [
     "DEFAULT_SEED_KEY", "seed_splitmix", "tonemap_rgba8", "comm_unique_id", "tile_layout",
     "place_tiles_host", "RT_RAYS_CHUNK", "RT_AOV_CENTER", "AovParams", "AovBuffers",
     "DenoiseParams", "DenoiseBuffers", "math_values", "math_sums", "PlanParams", "PlanStats",
-    "RT_PLAN_RELATIVE", "plan_samples_host",
+    "RT_PLAN_RELATIVE", "plan_samples_host", "PathParamsC",
 ]

@@ -175,6 +175,15 @@ class RayDomainInfo(ctypes.Structure):  # rt_ray_domain_info
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 8 and Ray.dir.offset == 16
 
 
+class PathParamsC(ctypes.Structure):  # rt_path_params
+    _fields_ = [("spp", ctypes.c_uint32), ("bounces", ctypes.c_uint32), ("sample_base", ctypes.c_uint32),
+                ("lanes_per_ray", ctypes.c_uint32), ("seed_key", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(PathParamsC) == 32 and PathParamsC.seed_key.offset == 16 and PathParamsC.flags.offset == 24
+
+
 class AovParams(ctypes.Structure):  # rt_aov_params
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("spp", "sample_base", "row_start", "row_step", "row_count", "flags")]
@@ -248,6 +257,9 @@ SIGNATURES = {
     "rt_render_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P]),
     "rt_trace_rays": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P]),
     "rt_trace_rays_async": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
+    "rt_path_params_default": (None, [ctypes.POINTER(PathParamsC)]),
+    "rt_trace_paths": (ctypes.c_int, [_P, ctypes.POINTER(PathParamsC), _P, _P, ctypes.c_uint64, _P, _P]),
+    "rt_trace_paths_async": (ctypes.c_int, [_P, ctypes.POINTER(PathParamsC), _P, _P, ctypes.c_uint64, _P, _P, _P]),
     "rt_render_aov": (ctypes.c_int, [_P, ctypes.POINTER(AovParams), ctypes.POINTER(AovBuffers)]),
     "rt_render_aov_async": (ctypes.c_int, [_P, ctypes.POINTER(AovParams), ctypes.POINTER(AovBuffers), _P]),
     "rt_denoise_params_default": (None, [ctypes.POINTER(DenoiseParams)]),

@@ -126,6 +126,7 @@ struct rt_ctx {
     DevBuf d_mis_part;             // per-ray MIS results of a split launch (rt_mis.hip)
     DevBuf d_out, d_out8;          // staging for host outputs (d_out8: the MIS integrator's RGBA8)
     DevBuf d_rays, d_hits;         // staging for host rays and hits (rt_trace_rays)
+    DevBuf d_ray_seeds, d_radiance;  // staging for host ray seeds and radiance (rt_trace_paths)
     DevBuf d_aov[3];               // staging for host feature buffers (rt_render_aov)
     DevBuf d_den[6];               // rt_denoise: the (D, V) ping-pong, then staging for the four host inputs
     DevBuf d_counts, d_totals;     // staging for host counts and totals (rt_render_counts, rt_plan_samples)
@@ -277,6 +278,30 @@ void set_tables(rt::KParams* K, const rt::SceneTables& t) {
     K->nTN = t.nTN;
     K->nC = t.nC;
     K->pair_free = t.pair_free;
+}
+
+// What every path kernel (render, counts, path query) takes from the context's
+// scene: a zeroed KParams with the tables, the shading records and the light.
+void set_scene(rt::KParams* K, const rt_ctx* c) {
+    memset(K, 0, sizeof(*K));
+    set_tables(K, c->tab);
+    K->tri_shade = c->d_scene[kTriShade].as<float4>();
+    K->light_mask = c->light_mask;
+    K->halton_tab = c->d_halton_tab.as<float>();
+    // both compact tables or neither: the launcher takes the sphere kernel when
+    // sph_lds is set, and that kernel's walks read sph_box (finish_scene)
+    K->sph_lds = c->sph_compact ? c->d_scene[kSphLds].as<uint32_t>() : nullptr;
+    K->sph_lds_id = c->d_scene[kSphLdsId].as<uint16_t>();
+    K->sph_shade = c->d_scene[kSphShade].as<float4>();
+    K->nE = c->scene.sph_lds_entries;
+    memcpy(K->light_center, c->scene.light.center, sizeof(K->light_center));
+    {  // rt_kernel.hip shade(): the sample point's zero terms drop out exactly unless -0 is involved
+        uint32_t by, bz;
+        memcpy(&by, &K->light_center[1], 4);
+        memcpy(&bz, &K->light_center[2], 4);
+        K->light_plain = (by != 0x80000000u && bz != 0x80000000u) ? 1u : 0u;
+    }
+    memcpy(K->light_color, c->scene.light.color, sizeof(K->light_color));
 }
 
 // The record arrays of c->scene on the device, for rt_create_ex (nothing
@@ -500,29 +525,11 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     }
 
     rt::KParams K;
-    memset(&K, 0, sizeof(K));
-    set_tables(&K, c->tab);
-    K.tri_shade = c->d_scene[kTriShade].as<float4>();
-    K.light_mask = c->light_mask;
-    K.halton_tab = c->d_halton_tab.as<float>();
-    // both compact tables or neither: the launcher takes the sphere kernel when
-    // sph_lds is set, and that kernel's walks read sph_box (finish_scene)
-    K.sph_lds = c->sph_compact ? c->d_scene[kSphLds].as<uint32_t>() : nullptr;
-    K.sph_lds_id = c->d_scene[kSphLdsId].as<uint16_t>();
-    K.sph_shade = c->d_scene[kSphShade].as<float4>();
+    set_scene(&K, c);
     K.seeds = c->d_seeds.as<uint32_t>();
     K.sum = sums ? c->d_sum.as<float4>() : nullptr;
     K.out = kout;
-    K.nE = c->scene.sph_lds_entries;
     set_camera(&K, c->scene.cam);
-    memcpy(K.light_center, c->scene.light.center, sizeof(K.light_center));
-    {  // rt_kernel.hip shade(): the sample point's zero terms drop out exactly unless -0 is involved
-        uint32_t by, bz;
-        memcpy(&by, &K.light_center[1], 4);
-        memcpy(&bz, &K.light_center[2], 4);
-        K.light_plain = (by != 0x80000000u && bz != 0x80000000u) ? 1u : 0u;
-    }
-    memcpy(K.light_color, c->scene.light.color, sizeof(K.light_color));
     K.spp = p->spp;
     K.sample_base = p->sample_base;
     K.row_start = start;
@@ -791,6 +798,84 @@ int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, r
     if (!dev && (st = copy_down(c, hits, khits, hit_bytes, stream, "hipMemcpyAsync(hits)")) != RT_OK) return st;
     if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
         return hip_fail(c, RT_ERR_LAUNCH, "ray_query execution", e);
+    return RT_OK;
+}
+
+// rt_trace_paths / rt_trace_paths_async: one launch of the path-query kernel
+// (rt_paths.hpp) over the context's tables and shading records.  Host pointers
+// go through the context's staging buffers on its own stream.
+int trace_paths_impl(rt_ctx* c, const rt_path_params* p, const rt_ray* rays, const uint32_t* seeds, uint64_t n,
+                     float* radiance, rt_ray_hit* first_hits, bool dev, hipStream_t stream, bool sync) {
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
+    if (n > 0x80000000ull) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: n > 2^31");
+    if (n == 0) return RT_OK;
+    if (!p || !rays || !radiance) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: params, rays or radiance is null");
+    if (p->spp < 1 || p->spp > (1u << 24)) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: spp must be in 1 .. 2^24");
+    if (p->bounces > RT_MAX_BOUNCES)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: bounces > 4: Halton dimensions would leave primes[24]");
+    if (p->lanes_per_ray != 0 && p->lanes_per_ray != 1 && p->lanes_per_ray != 16)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: lanes_per_ray must be 0, 1 or 16");
+    if ((1ull << 20) + p->sample_base + p->spp > (1ull << 32))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: 2^20 + sample_base + spp passes 2^32 (the Halton index wraps)");
+    if (p->flags & ~(uint32_t)RT_OUT_DEVICE) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: unknown flags bits");
+    if (p->reserved != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_trace_paths: reserved must be 0");
+    hipError_t e;
+    int st;
+    const size_t ray_bytes = (size_t)n * sizeof(rt_ray), hit_bytes = (size_t)n * sizeof(rt_ray_hit);
+    const size_t seed_bytes = (size_t)n * sizeof(uint32_t), rad_bytes = (size_t)n * 4 * sizeof(float);
+    rt::PathQueryArgs A{};
+    A.rays = reinterpret_cast<const float4*>(rays);
+    A.seeds = seeds;
+    A.radiance = reinterpret_cast<float4*>(radiance);
+    A.hits = reinterpret_cast<uint2*>(first_hits);
+    if (!dev) {
+        if ((st = reserve(c, c->d_rays, ray_bytes, "hipMalloc(ray staging)")) != RT_OK ||
+            (st = reserve(c, c->d_radiance, rad_bytes, "hipMalloc(radiance staging)")) != RT_OK)
+            return st;
+        A.rays = c->d_rays.as<float4>();
+        A.radiance = c->d_radiance.as<float4>();
+        if ((e = hipMemcpyAsync(c->d_rays.as<void>(), rays, ray_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess)
+            return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(rays)", e);
+        if (seeds) {
+            if ((st = reserve(c, c->d_ray_seeds, seed_bytes, "hipMalloc(ray seed staging)")) != RT_OK) return st;
+            A.seeds = c->d_ray_seeds.as<uint32_t>();
+            if ((e = hipMemcpyAsync(c->d_ray_seeds.as<void>(), seeds, seed_bytes, hipMemcpyHostToDevice, stream)) !=
+                hipSuccess)
+                return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(ray seeds)", e);
+        }
+        if (first_hits) {
+            if ((st = reserve(c, c->d_hits, hit_bytes, "hipMalloc(hit staging)")) != RT_OK) return st;
+            A.hits = c->d_hits.as<uint2>();
+        }
+    }
+    A.n = (uint32_t)n;
+    A.seed_key = p->seed_key;
+    A.dom = rt::ray_domain(c->scene.extent);
+    rt::KParams K;
+    set_scene(&K, c);
+    K.spp = p->spp;
+    K.sample_base = p->sample_base;
+    K.lanes = p->lanes_per_ray;
+    // every seed is masked to 20 bits: the bound needs no look at device memory
+    K.max_index = 0xFFFFFu + p->sample_base + (p->spp - 1u);
+    if ((st = timed_launch(c, stream, "path_query", &c->launch, [&](rt::LaunchInfo* info) {
+             return rt::launch_path_query(K, A, p->bounces, c->scene_mem, stream, info);
+         })) != RT_OK)
+        return st;
+    if (!dev) {
+        if ((st = copy_down(c, radiance, A.radiance, rad_bytes, stream, "hipMemcpyAsync(radiance)")) != RT_OK) return st;
+        if (first_hits &&
+            (st = copy_down(c, first_hits, A.hits, hit_bytes, stream, "hipMemcpyAsync(first hits)")) != RT_OK)
+            return st;
+    }
+    if (sync) {
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess)
+            return hip_fail(c, RT_ERR_LAUNCH, "path_query execution", e);
+        uint32_t short_end = 0;  // RT_LDS_CHECK builds (rt_kernel.hip)
+        if (rt::lds_check_result(&short_end) == hipSuccess && short_end)
+            return fail(c, RT_ERR_LAUNCH, "LDS overflow: staged records end at byte " + std::to_string(short_end) +
+                                              ", past the dispatch's dynamic LDS");
+    }
     return RT_OK;
 }
 
@@ -1228,6 +1313,22 @@ int rt_trace_rays_async(rt_ctx* c, const rt_ray* rays_dev, uint64_t n, uint32_t 
     if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
     DeviceGuard g(c->device);
     return trace_rays_impl(c, rays_dev, n, flags, hits_dev, true, (hipStream_t)hip_stream, false);
+}
+
+int rt_trace_paths(rt_ctx* c, const rt_path_params* p, const rt_ray* rays, const uint32_t* seeds, uint64_t n,
+                   float* radiance, rt_ray_hit* first_hits) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return trace_paths_impl(c, p, rays, seeds, n, radiance, first_hits, p && (p->flags & RT_OUT_DEVICE), c->stream,
+                            true);
+}
+
+int rt_trace_paths_async(rt_ctx* c, const rt_path_params* p, const rt_ray* rays_dev, const uint32_t* seeds_dev,
+                         uint64_t n, float* radiance_dev, rt_ray_hit* first_hits_dev, void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return trace_paths_impl(c, p, rays_dev, seeds_dev, n, radiance_dev, first_hits_dev, true, (hipStream_t)hip_stream,
+                            false);
 }
 
 int rt_render_aov(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b) {

@@ -281,6 +281,13 @@ void rt_denoise_params_default(rt_denoise_params* p) {
     p->depth_floor = 0.01f;
 }
 
+void rt_path_params_default(rt_path_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->spp = 1;
+    p->bounces = 3;
+}
+
 int rt_scene_describe(const rt_scene_desc* d, rt_scene_info* info) {
     return rt_scene_describe_ex(d, nullptr, info);
 }

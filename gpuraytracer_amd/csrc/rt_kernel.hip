@@ -104,7 +104,12 @@ struct PathState {
 // (fused_shadow_closest); the next hit is returned in *nid / *nt.
 // STASH (the one-wave sphere kernel): contrib and the next direction wait in
 // the per-lane LDS stash sv.xstash across the shadow walk.
-template <int b, int B, int GEO, bool SPH, bool SMALL, bool FUSE = false, bool STASH = false>
+// COH: the wave's rays are the coherent camera rays of a tile, the render
+// kernels' bounce 0: the triangle BVH's shadow query walks as a wave packet
+// and keeps every lane.  The path-query kernel (rt_paths.hpp) shades the
+// caller's rays at bounce 0 without it.
+template <int b, int B, int GEO, bool SPH, bool SMALL, bool FUSE = false, bool STASH = false,
+          bool COH = (b == 0)>
 __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, PathState& s, int id,
                                       float t, int* nid = nullptr, float* nt = nullptr) {
     f3 N, right, fwd, diffuse;
@@ -251,7 +256,7 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
     // ceiling): Cornell +4.3 %, 1000 spheres +1.8 %, 100k triangles +2.5 %.
     // Bounce-0 shadow rays of the triangle BVH walk as wave packets and keep
     // every lane (skipping there: 100k triangles -8 %).
-    const bool lit = (GEO == kGeoTriBvh && b == 0) || contrib.x != 0.0f || contrib.y != 0.0f ||
+    const bool lit = (GEO == kGeoTriBvh && COH) || contrib.x != 0.0f || contrib.y != 0.0f ||
                      contrib.z != 0.0f;
     if constexpr (STASH) {
         // the sphere kernel parks contrib and the next direction in a per-lane
@@ -271,7 +276,7 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
             st[5 * SS + t] = d2.z;
         }
         const bool occluded =
-            lit && any_hit<GEO, SPH, b == 0 && !SPH>(sv, p, L, 0.0f, dist - 1e-3f, seg_lo, seg_hi);  // :79-85
+            lit && any_hit<GEO, SPH, COH && !SPH>(sv, p, L, 0.0f, dist - 1e-3f, seg_lo, seg_hi);  // :79-85
         uint32_t t2 = threadIdx.x;
         asm volatile("" : "+v"(t2));
         if (lit && !occluded)                              // :87-89
@@ -285,11 +290,11 @@ __device__ __forceinline__ bool shade(const KParams& P, const SceneView& sv, Pat
 #if RT_CENSUS == 3
     if (lit) {
         f3 p2 = cz(p), L2 = cz(L);
-        cz_sink(any_hit<GEO, SPH, b == 0 && !SPH>(sv, p2, L2, 0.0f, cz(dist) - 1e-3f, cz(seg_lo), cz(seg_hi)) ? 1.0f
+        cz_sink(any_hit<GEO, SPH, COH && !SPH>(sv, p2, L2, 0.0f, cz(dist) - 1e-3f, cz(seg_lo), cz(seg_hi)) ? 1.0f
                                                                                                             : 0.0f);
     }
 #endif
-    if (lit && !any_hit<GEO, SPH, b == 0 && !SPH>(sv, p, L, 0.0f, dist - 1e-3f, seg_lo, seg_hi))  // :79-85
+    if (lit && !any_hit<GEO, SPH, COH && !SPH>(sv, p, L, 0.0f, dist - 1e-3f, seg_lo, seg_hi))  // :79-85
         s.acc = s.acc + contrib;                           // :87-89
     if (b + 1 < B) {
         s.d = d2;
@@ -350,18 +355,18 @@ struct BounceChain<B, B, GEO, SPH, SMALL> {
 };
 
 // Fused bounce chain: enters bounce b with the closest hit (id, t) of its ray.
-template <int b, int B, int GEO, bool SMALL>
+template <int b, int B, int GEO, bool SMALL, bool COH = (b == 0)>
 struct FusedChain {
     __device__ __forceinline__ static void run(const KParams& P, const SceneView& sv,
                                                PathState& s, int id, float t) {
         int nid = -1;
         float nt = 0.0f;
-        if (!shade<b, B, GEO, false, SMALL, true>(P, sv, s, id, t, &nid, &nt)) return;
+        if (!shade<b, B, GEO, false, SMALL, true, false, COH>(P, sv, s, id, t, &nid, &nt)) return;
         if (b + 1 < B && nid >= 0) FusedChain<b + 1, B, GEO, SMALL>::run(P, sv, s, nid, nt);
     }
 };
-template <int B, int GEO, bool SMALL>
-struct FusedChain<B, B, GEO, SMALL> {
+template <int B, int GEO, bool SMALL, bool COH>
+struct FusedChain<B, B, GEO, SMALL, COH> {
     __device__ __forceinline__ static void run(const KParams&, const SceneView&, PathState&, int,
                                                float) {}
 };
@@ -1235,6 +1240,8 @@ hipError_t launch_path_trace(const KParams& P, uint32_t bounces, SceneMem mem,
 
 // the render with per-pixel sample counts: after every kernel and launcher above
 #include "rt_counts.hpp"
+// path-traced radiance along the caller's own rays: after the counts kernels
+#include "rt_paths.hpp"
 
 hipError_t lds_check_result(uint32_t* end) {
     *end = 0;

@@ -296,6 +296,54 @@ struct RayQueryParams {
 };
 hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info);
 
+// ---- path queries (rt_paths.hpp; include/rtpt.h rt_trace_paths) -------------
+// What rt_trace_paths adds to KParams (extra kernel arguments of
+// path_query_kernel; KParams is not regrouped, see above).  Of P the kernel
+// reads the tables, the shading records, the light, halton_tab, spp,
+// sample_base; the launcher also max_index (the host's bound 0xFFFFF +
+// sample_base + spp - 1 of every index) and lanes (0 = auto, 1 or 16 lanes per
+// ray).  No camera, no seeds of the context, no sums.
+struct PathQueryArgs {
+    const float4* rays;        // 2 float4 per ray: (origin, tmin) (dir, tmax), device memory
+    const uint32_t* seeds;     // one per ray (the low 20 bits are used), or null: splitmix64(seed_key + r)
+    float4* radiance;          // (sum / spp, 1) per ray; (0, 0, 0, 0) for a ray outside the domain
+    uint2* hits;               // (t bits, id) of the first segment per ray, or null
+    uint32_t n;                // rays, 1 .. 2^31
+    uint64_t seed_key;
+    RayDomain dom;             // rt_raydomain.h
+};
+// Automatic lanes per ray (fixed-digit indices only; one lane otherwise): 16
+// from 16 samples per ray on, from 8 on for at most 65,536 rays and from 4 on
+// for at most 4,096 rays, where one lane per ray leaves most of the device
+// idle.  Every cell of the table measured over spp and ray count on three
+// scenes agrees (tools/bench_paths.py, profiles/r21/paths.md).
+constexpr bool path_auto_lanes16(uint32_t spp, uint32_t n) {
+    return spp >= 16u || (spp >= 8u && n <= 65536u) || (spp >= 4u && n <= 4096u);
+}
+// halton_tables_on for the path-query kernel, always inlined.  The largest
+// instantiations of the render kernels call halton_tables_on out of line, and
+// that copy is specialised for its callers: one more device caller changes it
+// and them (tools/isa_diff.sh).
+__host__ __device__ __forceinline__ constexpr bool path_query_tables_on(int geo, bool small, uint32_t spp, uint32_t L) {
+    return geo == kLayPairClu && small && (spp + L - 1) / L >= kHaltonTabMinRounds;
+}
+static_assert(path_query_tables_on(kLayPairClu, true, 128, 16) == halton_tables_on(kLayPairClu, true, 128, 16) &&
+                  path_query_tables_on(kLayPairClu, true, 127, 16) == halton_tables_on(kLayPairClu, true, 127, 16) &&
+                  path_query_tables_on(kLayPairClu, false, 128, 1) == halton_tables_on(kLayPairClu, false, 128, 1) &&
+                  path_query_tables_on(kLayPairLds, true, 128, 1) == halton_tables_on(kLayPairLds, true, 128, 1) &&
+                  path_query_tables_on(kLayPairClu, true, 8, 1) == halton_tables_on(kLayPairClu, true, 8, 1) &&
+                  path_query_tables_on(kLayPairClu, true, 7, 1) == halton_tables_on(kLayPairClu, true, 7, 1),
+              "one rule for the Halton tables");
+// THE dynamic LDS of a path-query workgroup of layout `lay` (after
+// ray_query_layout): staged_f4, then the Halton tables when the launch copies
+// them (halton_tables_on).  The kernel places its arrays by these terms and the
+// launcher requests exactly this.
+__host__ __device__ constexpr size_t path_query_lds_bytes(int lay, uint32_t nT, uint32_t nP, uint32_t nC, bool tables) {
+    return ray_query_lds_bytes(lay, nT, nP, nC) + (tables ? (size_t)4 * kHaltonTabLdsFloats : (size_t)0);
+}
+hipError_t launch_path_query(const KParams& P, const PathQueryArgs& A, uint32_t bounces, SceneMem mem,
+                             hipStream_t stream, LaunchInfo* info);
+
 // ---- first-hit feature buffers (rt_aov.hip; include/rtpt.h rt_render_aov) ---
 constexpr uint32_t kAovCenter = 0x400u;  // RT_AOV_CENTER
 // The AOV kernel draws Halton dimensions 0 and 1 only; dimension 0 is a bit

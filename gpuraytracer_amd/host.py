@@ -21,7 +21,7 @@ import numpy as np
 from ._native import (MATH_FNS, RT_MATH_DEVICE, RT_MATH_HOST, RT_MATH_VALUES_MAX, LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, RT_UPDATE_REBUILD, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
-                      PlanParams, PlanStats, RT_PLAN_RELATIVE, RenderParamsC,
+                      PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, RenderParamsC,
                       RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, UpdateStats, float3,
                       lib)
 
@@ -613,6 +613,85 @@ class Renderer:
         if cur is not None:
             cur.synchronize()
         return hits[:, 0].view(torch.float32), hits[:, 1]
+
+    def trace_paths(self, rays, spp: int = 1, bounces: int = 3, sample_base: int = 0, seeds=None,
+                    seed_key: int = DEFAULT_SEED_KEY, lanes: int = 0, first_hits: bool = False, out=None,
+                    stream=None):
+        """Path-traced radiance along the caller's rays (rt_trace_paths,
+        DESIGN.md §3.28): ``rays`` is (n, 8) float32 as for :meth:`trace_rays`;
+        ray r draws samples ``[sample_base, sample_base + spp)`` of the Halton
+        index ``(seeds[r] & 0xFFFFF) + n`` (``seeds=None``: the value
+        ``seed_splitmix(n, 1, seed_key)`` gives r) and the result is the
+        (n, 4) float32 mean radiance with alpha 1; a ray outside the exactness
+        domain is not traced and gets (0, 0, 0, 0).  ``lanes``: 0 (automatic),
+        1 or 16 lanes per ray.  ``first_hits=True`` also returns the first
+        segment's ``(t, id)`` as :meth:`trace_rays` gives it.
+
+        Numpy arrays give numpy results synchronously.  Torch tensors on the
+        context's device take the device path: ``out`` is an (n, 4) float32
+        tensor, or with ``first_hits`` a pair of it and an (n, 2) int32 tensor;
+        with ``stream`` the call is enqueued there without a host sync."""
+        p = PathParamsC()
+        lib.rt_path_params_default(ctypes.byref(p))
+        p.spp, p.bounces, p.sample_base, p.lanes_per_ray, p.seed_key = spp, bounces, sample_base, lanes, seed_key
+        out_rad, out_hits = (out if isinstance(out, (tuple, list)) else (out, None))
+        if isinstance(rays, np.ndarray):
+            r = np.ascontiguousarray(rays, dtype=np.float32)
+            if r.ndim != 2 or r.shape[1] != 8:
+                raise ValueError("rays must have shape (n, 8)")
+            n = r.shape[0]
+            sd = None
+            if seeds is not None:
+                sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+                if sd.shape[0] != n:
+                    raise ValueError("seeds must hold one value per ray")
+            rad = np.empty((n, 4), np.float32) if out_rad is None else out_rad
+            if rad.dtype != np.float32 or rad.shape != (n, 4) or not rad.flags.c_contiguous:
+                raise ValueError("out must be a contiguous (n, 4) float32 array")
+            hits = None
+            if first_hits:
+                hits = np.empty((n, 2), np.int32) if out_hits is None else out_hits
+                if hits.dtype != np.int32 or hits.shape != (n, 2) or not hits.flags.c_contiguous:
+                    raise ValueError("the first hits must be a contiguous (n, 2) int32 array")
+            _check(lib.rt_trace_paths(self._ctx, ctypes.byref(p), r.ctypes.data_as(ctypes.c_void_p),
+                                      None if sd is None else sd.ctypes.data_as(ctypes.c_void_p), n,
+                                      rad.ctypes.data_as(ctypes.c_void_p),
+                                      None if hits is None else hits.ctypes.data_as(ctypes.c_void_p)), self._ctx)
+            return (rad, (hits[:, 0].view(np.float32), hits[:, 1])) if first_hits else rad
+        import torch  # plumbing only: device memory and the caller's stream
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("rays must be a contiguous (n, 8) float32 tensor")
+        if not rays.is_cuda or rays.device.index != self.device:
+            raise ValueError("rays must live on the context's device")
+        n = rays.shape[0]
+
+        def on_device(t, dtype, shape, what):
+            if (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != rays.device):
+                raise ValueError(f"{what} must be a contiguous {shape} {dtype} tensor on the rays' device")
+            return t
+
+        sd_ptr = None
+        if seeds is not None:  # int32 tensors carry the 32 bits (torch has little uint32 support)
+            if seeds.dtype not in (torch.int32, torch.uint32):
+                raise ValueError("seeds must be an int32 or uint32 tensor")
+            sd_ptr = on_device(seeds, seeds.dtype, (n,), "seeds").data_ptr()
+        rad = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if out_rad is None else out_rad
+        on_device(rad, torch.float32, (n, 4), "out")
+        hits = None
+        if first_hits:
+            hits = torch.empty((n, 2), dtype=torch.int32, device=rays.device) if out_hits is None else out_hits
+            on_device(hits, torch.int32, (n, 2), "the first hits")
+        p.flags = RT_OUT_DEVICE
+        cur = torch.cuda.current_stream(rays.device) if stream is None else None
+        handle = cur.cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        _check(lib.rt_trace_paths_async(self._ctx, ctypes.byref(p), ctypes.c_void_p(rays.data_ptr()),
+                                        None if sd_ptr is None else ctypes.c_void_p(sd_ptr), n,
+                                        ctypes.c_void_p(rad.data_ptr()),
+                                        None if hits is None else ctypes.c_void_p(hits.data_ptr()),
+                                        ctypes.c_void_p(handle)), self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        return (rad, (hits[:, 0].view(torch.float32), hits[:, 1])) if first_hits else rad
 
     def render_aov(self, spp: int = 1, sample_base: int = 0, row_start: int = 0, row_step: int = 1,
                    row_count: int = 0, center: bool = False, albedo: bool = True,

@@ -250,7 +250,8 @@ int rt_place_tiles_host(const void* gathered, int32_t width, int32_t height, int
                         uint32_t flags, void* frame);
 
 /* Which kernel instantiation the most recent rt_render/rt_render_async,
- * rt_trace_rays/rt_trace_rays_async, rt_render_aov/rt_render_aov_async or
+ * rt_trace_rays/rt_trace_rays_async, rt_trace_paths/rt_trace_paths_async,
+ * rt_render_aov/rt_render_aov_async or
  * rt_denoise/rt_denoise_async (its last pass) launched, with its launch shape:
  * lets a caller (bench, tests) state which configuration it timed or checked.  `kernel` is the demangled name rocprofv3
  * reports, e.g. "rt::path_trace_kernel<3, 6, false, true, 4>". */
@@ -548,6 +549,82 @@ int rt_plan_samples_async(rt_ctx* ctx, const rt_plan_params* params, const float
  * params->rows (>= 1) rows of `width` pixels.  RT_OUT_DEVICE is not accepted. */
 int rt_plan_samples_host(int32_t width, const rt_plan_params* params, const float* first, const float* all,
                          uint32_t* counts, rt_plan_stats* stats);
+
+/* ---- path queries: radiance along the caller's own rays ---------------------
+ * rt_trace_rays answers geometry for the caller's rays; rt_trace_paths answers
+ * light: the render's path tracer started on ray r
+ * instead of a camera ray.  Light probes, lightmap and vertex
+ * baking, irradiance caches, reflection and off-screen lookups.  These entry
+ * points were added without a change of RTPT_ABI_VERSION (nothing else
+ * changed): a caller that may meet an older library detects the feature by the
+ * presence of the symbol rt_trace_paths (dlsym).
+ *
+ * Seed: s_r = seeds[r] & 0xFFFFF (only the low 20 bits of a supplied seed are
+ * used); with seeds == NULL, s_r = splitmix64(seed_key + r) mod 2^20, the value
+ * rt_fill_seeds(seed_key) gives pixel r.
+ * First segment: the closest hit of the ray with tmin < t < tmax strictly, ties
+ * to the lowest id: what rt_trace_rays returns for that ray.  It is the same
+ * for every sample.
+ * Samples: for n in [sample_base, sample_base + spp), i = s_r + n, the bounce
+ * loop of the render for b = 0 .. bounces-1: bounce 0's hit is the first
+ * segment, bounces >= 1 query with tmin 0.001 / tmax 1000, the Halton
+ * dimensions are the render's 2+5b .. 5+5b (dimensions 0 and 1, the camera
+ * jitter, are not drawn).
+ * Sum: in fp32 in ascending n from +0; radiance[r] = (sum / (float)spp, 1.0f).
+ * So a ray that equals the camera ray of pixel p, sample n, with tmin 0.001 and
+ * tmax 1000, traced with seeds[r] = seed[p], spp = 1 and sample_base = n, gives
+ * that sample's radiance of rt_render bit for bit.
+ *
+ * A ray outside the exactness domain (rt_debug_ray_domain: any NaN or infinity,
+ * a far origin, a direction length outside [1/2, 2], tmin < 0, tmin >= tmax,
+ * tmax > 1000) is not traced: radiance[r] = (0, 0, 0, 0) -- alpha 0 tells it
+ * from a traced miss, whose alpha is 1 -- and first_hits[r] = (tmax bit for
+ * bit, -1).  The call is total: any 32 bytes are a ray, and no value from a ray
+ * or a seed is used as an index.  From the first hit on the path is the
+ * render's own, with the accelerated layouts' one known limit (a ray lying in
+ * an oblique triangle's plane to rounding, see rt_trace_rays).
+ * first_hits (optional): for every in-domain ray the answer of rt_trace_rays
+ * (closest hit). */
+typedef struct rt_path_params {
+    uint32_t spp;            /* 1 .. 2^24                                    */
+    uint32_t bounces;        /* 0 .. RT_MAX_BOUNCES                          */
+    uint32_t sample_base;    /* 2^20 + sample_base + spp must not pass 2^32  */
+    uint32_t lanes_per_ray;  /* 0 = auto, 1 or 16                            */
+    uint64_t seed_key;       /* used when seeds == NULL                      */
+    uint32_t flags;          /* RT_OUT_DEVICE                                */
+    uint32_t reserved;       /* must be 0                                    */
+} rt_path_params; /* 32 B */
+
+/* spp 1, bounces 3, everything else 0. */
+void rt_path_params_default(rt_path_params* params);
+
+/* Trace n rays and block until done.  rays, seeds (optional), radiance (n * 4
+ * floats) and first_hits (optional) are host memory (the context's staging
+ * buffers carry them), or all device memory with RT_OUT_DEVICE.  n == 0 is
+ * RT_OK without a launch.  RT_ERR_INVALID_ARG, with an rt_last_error message
+ * that names the field: n > 2^31; a NULL params, rays or radiance with n > 0;
+ * spp outside 1 .. 2^24; bounces > RT_MAX_BOUNCES; lanes_per_ray not 0, 1 or
+ * 16; 2^20 + sample_base + spp > 2^32; an unknown flag bit; nonzero reserved.
+ * RT_ERR_STATE: a context a failed rt_update_scene left broken.  No context
+ * seeds are needed; rt_create_options' lanes_per_pixel and walk_scheduler are
+ * ignored, and a context of RT_WALK_FREE, RT_WALK_SORTED or RT_LAYOUT_SORTED
+ * runs through its lockstep form.
+ * The kernel is rt::path_query_kernel<B, layout, spheres, small, L>
+ * (rt_last_launch, with its grid, block, dynamic LDS and whether the Halton
+ * tables were copied; lanes_per_pixel reports L).  L lanes trace one ray's
+ * samples: 16 (one DPP row) needs fixed-digit Halton indices (0xFFFFF +
+ * sample_base + spp - 1 < 3^13) and is taken when lanes_per_ray is 16, or
+ * automatically from spp >= 16 on, from 8 on for n <= 65536 and from 4 on for
+ * n <= 4096 (measured); otherwise one lane traces the ray.
+ * The result does not depend on L.  rt_last_kernel_ms gives the device time. */
+int rt_trace_paths(rt_ctx* ctx, const rt_path_params* params, const rt_ray* rays, const uint32_t* seeds,
+                   uint64_t n, float* radiance, rt_ray_hit* first_hits);
+
+/* Asynchronous variant: all pointers are device memory, the kernel is enqueued
+ * on `hip_stream` (a hipStream_t, NULL = the null stream).  No host sync. */
+int rt_trace_paths_async(rt_ctx* ctx, const rt_path_params* params, const rt_ray* rays_dev,
+                         const uint32_t* seeds_dev, uint64_t n, float* radiance_dev, rt_ray_hit* first_hits_dev,
+                         void* hip_stream);
 
 /* The exactness domain of a scene (host-only, no device): a ray is in it when
  * all eight floats are finite, max |origin component| <= origin_max,
