@@ -231,6 +231,14 @@ class PlanStats(ctypes.Structure):  # rt_plan_stats
 assert ctypes.sizeof(PlanParams) == 40 and ctypes.sizeof(PlanStats) == 32
 
 
+class WaveMask(ctypes.Structure):  # rt_wave_mask
+    _fields_ = [(n, ctypes.c_uint32) for n in ("cam_mask", "shd_mask", "shd_cskip", "shd_available")] + \
+               [(n, ctypes.c_int32) for n in ("x0", "x1", "y0", "y1")]
+
+
+assert ctypes.sizeof(WaveMask) == 32
+
+
 class MisParamsC(ctypes.Structure):  # rt_mis_params
     _fields_ = [(n, ctypes.c_uint32) for n in
                 ("camera_rays", "mis_samples", "row_start", "row_step", "row_count", "flags")]
@@ -336,6 +344,11 @@ SIGNATURES = {
                                            ctypes.c_uint32]),
     "rt_debug_halton_table": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _P, _P]),
     "rt_debug_halton_table_device": (ctypes.c_int, [_P, _P, ctypes.c_uint32]),
+    "rt_debug_wave_rects": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32] + [ctypes.c_uint32] * 4 +
+                            [_P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "rt_debug_wave_masks": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), ctypes.c_uint32, _P, ctypes.c_uint32,
+                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
 }
 
 

@@ -92,6 +92,26 @@ enum SceneArray {
     kSphIsect, kSphShade, kSphNodes, kSphPerm, kMisShade, kSceneArrays
 };
 
+// Everything the per-wave masks of a launch depend on (rt_ctx::d_wave_masks):
+// the camera, the light centre, the scene's tables (the epoch counts their
+// updates), the frame, the row partition and the wave geometry.  Compared
+// with memcmp: zero it before filling.
+struct MaskKey {
+    float cam[14];  // pos, u, v, w, halfW, halfH
+    float light_center[3];
+    int32_t W, H;
+    uint32_t row_start, row_step, row_count;
+    uint32_t L, wave_w, wave_h;
+    uint64_t scene_epoch;
+};
+
+// A stream that has a render in flight (or finished) that reads the mask
+// table, and the event recorded after its last such render.
+struct MaskReader {
+    hipStream_t stream;
+    hipEvent_t done;
+};
+
 }  // namespace
 
 // Teardown is the destructor and the members' own, in this order (all with
@@ -116,6 +136,15 @@ struct rt_ctx {
     bool sph_compact = false;        // rt_scene.hpp sphere_compact_usable: the sphere kernel's tables exist
     uint64_t light_mask = 0;         // rt_scene.hpp light_mask: the box-cluster kernel's light flags
     DevBuf d_halton_tab;             // the Halton low-digit tables (rt_halton.hpp), filled once by rt_create_ex
+    // The per-wave candidate masks of ONE launch geometry (rt_kernel.hpp WaveMask):
+    // filled by the first render launch of that geometry, reused while mask_key matches.
+    DevBuf d_wave_masks;
+    MaskKey mask_key{};              // what the table was filled for (valid: d_wave_masks holds it)
+    bool mask_valid = false;
+    uint64_t scene_epoch = 0;        // counts rt_update_scene: the tables the masks were computed from
+    uint64_t mask_fills = 0;         // launches of the fill kernel (rt_debug_wave_masks reports it)
+    Event ev_mask_fill;              // end of the last fill
+    std::vector<MaskReader> mask_readers;  // the streams whose renders may still read the table
     uint32_t tri_bvh_build_used = 0; // rt_tri_bvh_build of the built tree (0: none)
     uint32_t tri_leaf_max = 1;       // triangles per leaf at most in the built tree (rt_debug_tri_bvh)
     float tri_bvh_build_ms = 0.0f;   // wall time of the triangle-BVH build
@@ -166,6 +195,7 @@ struct rt_ctx {
     ~rt_ctx() {
         if (tiles_pending) (void)hipEventSynchronize(ev_tiles);  // a gather may still read d_tile
         if (comm) (void)ncclCommDestroy(comm);                   // before d_tile and d_gather go
+        for (const MaskReader& r : mask_readers) (void)hipEventDestroy(r.done);
     }
 };
 
@@ -433,13 +463,95 @@ void finish_scene(rt_ctx* c) {
 // Resolves row partition defaults and validates it against the frame height.
 bool resolve_rows(const rt_ctx* c, uint32_t row_start, uint32_t row_step, uint32_t row_count, uint32_t* start,
                   uint32_t* step, uint32_t* count) {
-    const uint32_t H = (uint32_t)c->scene.cam.H;
-    *start = row_start;
-    *step = row_step ? row_step : 1u;
-    if (*start >= H) return false;
-    const uint32_t avail = (H - 1u - *start) / *step + 1u;
-    *count = row_count ? row_count : avail;
-    return *count <= avail;
+    return rtapi::resolve_rows((uint32_t)c->scene.cam.H, row_start, row_step, row_count, start, step, count);
+}
+
+// What a render launch takes from its parameters and the context's options:
+// the camera, the samples, the resolved row partition and the launch choices.
+void set_launch(rt::KParams* K, const rt_ctx* c, const rt_render_params* p, uint32_t start, uint32_t step,
+                uint32_t count) {
+    set_camera(K, c->scene.cam);
+    K->spp = p->spp;
+    K->sample_base = p->sample_base;
+    K->row_start = start;
+    K->row_step = step;
+    K->row_count = count;
+    K->lanes = c->lanes;
+    K->walk = c->walk;
+    K->walk_leaf_den = c->walk_leaf_den;
+}
+
+// The per-wave masks of the launch (K, g) in the context's table, K->wave_masks
+// set to it.  The table is reused while its key matches;
+// otherwise the fill is enqueued on `stream`, after every render that may still
+// read the old table on any stream.  A launch on another stream than the fill's
+// waits for the fill.
+int ensure_wave_masks(rt_ctx* c, rt::KParams* K, const rt::WaveGrid& g, hipStream_t stream) {
+    MaskKey key;
+    memset(&key, 0, sizeof(key));
+    memcpy(key.cam, K->cam_pos, sizeof(K->cam_pos));
+    memcpy(key.cam + 3, K->cam_u, sizeof(K->cam_u));
+    memcpy(key.cam + 6, K->cam_v, sizeof(K->cam_v));
+    memcpy(key.cam + 9, K->cam_w, sizeof(K->cam_w));
+    key.cam[12] = K->halfW;
+    key.cam[13] = K->halfH;
+    memcpy(key.light_center, K->light_center, sizeof(key.light_center));
+    key.W = K->W;
+    key.H = K->H;
+    key.row_start = K->row_start;
+    key.row_step = K->row_step;
+    key.row_count = K->row_count;
+    key.L = g.L;
+    key.wave_w = g.wave_w;
+    key.wave_h = g.wave_h;
+    key.scene_epoch = c->scene_epoch;
+    hipError_t e;
+    if (!c->ev_mask_fill.h && (e = hipEventCreateWithFlags(&c->ev_mask_fill.h, hipEventDisableTiming)) != hipSuccess)
+        return hip_fail(c, RT_ERR_OUT_OF_MEMORY, "hipEventCreate(mask fill)", e);
+    const size_t bytes = (size_t)g.waves_x * g.waves_y * sizeof(rt::WaveMask);
+    if (!c->mask_valid || memcmp(&key, &c->mask_key, sizeof(key)) != 0 || c->d_wave_masks.bytes() < bytes) {
+        c->mask_valid = false;
+        for (const MaskReader& r : c->mask_readers)
+            if ((e = hipStreamWaitEvent(stream, r.done, 0)) != hipSuccess)
+                return hip_fail(c, RT_ERR_LAUNCH, "hipStreamWaitEvent(mask table readers)", e);
+        // and the last fill, which waited for the readers before it: the readers start over
+        if ((e = hipStreamWaitEvent(stream, c->ev_mask_fill, 0)) != hipSuccess)
+            return hip_fail(c, RT_ERR_LAUNCH, "hipStreamWaitEvent(mask table fill)", e);
+        for (const MaskReader& r : c->mask_readers) (void)hipEventDestroy(r.done);
+        c->mask_readers.clear();
+        int st;  // a table that has to grow is freed first, which waits for the device
+        if ((st = reserve(c, c->d_wave_masks, bytes, "hipMalloc(wave masks)")) != RT_OK) return st;
+        if ((e = rt::launch_wave_masks(*K, g, c->d_wave_masks.as<uint4>(), stream)) != hipSuccess)
+            return hip_fail(c, RT_ERR_LAUNCH, "wave_masks launch", e);
+        if ((e = hipEventRecord(c->ev_mask_fill, stream)) != hipSuccess)
+            return hip_fail(c, RT_ERR_LAUNCH, "hipEventRecord(mask fill)", e);
+        c->mask_key = key;
+        c->mask_valid = true;
+        ++c->mask_fills;
+    } else if ((e = hipStreamWaitEvent(stream, c->ev_mask_fill, 0)) != hipSuccess) {
+        return hip_fail(c, RT_ERR_LAUNCH, "hipStreamWaitEvent(mask table fill)", e);
+    }
+    K->wave_masks = c->d_wave_masks.as<uint4>();
+    return RT_OK;
+}
+
+// After a render on `stream` that reads the mask table: the event a later
+// refill on any stream waits for.
+int note_mask_reader(rt_ctx* c, hipStream_t stream) {
+    MaskReader* r = nullptr;
+    for (MaskReader& q : c->mask_readers)
+        if (q.stream == stream) r = &q;
+    hipError_t e;
+    if (!r) {
+        hipEvent_t ev = nullptr;
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess)
+            return hip_fail(c, RT_ERR_OUT_OF_MEMORY, "hipEventCreate(mask reader)", e);
+        c->mask_readers.push_back(MaskReader{stream, ev});
+        r = &c->mask_readers.back();
+    }
+    if ((e = hipEventRecord(r->done, stream)) != hipSuccess)
+        return hip_fail(c, RT_ERR_LAUNCH, "hipEventRecord(mask reader)", e);
+    return RT_OK;
 }
 
 // What rt_render_counts adds to a render: one count per pixel in, the totals out.
@@ -529,20 +641,18 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     K.seeds = c->d_seeds.as<uint32_t>();
     K.sum = sums ? c->d_sum.as<float4>() : nullptr;
     K.out = kout;
-    set_camera(&K, c->scene.cam);
-    K.spp = p->spp;
-    K.sample_base = p->sample_base;
-    K.row_start = start;
-    K.row_step = step;
-    K.row_count = count;
+    set_launch(&K, c, p, start, step, count);
     K.accumulate = p->accumulate ? 1u : 0u;
     K.samples_total = (uint32_t)total;
     K.flags = ((p->flags & RT_OUT_FP16) ? rt::kOutFp16 : 0u) | ((p->flags & RT_OUT_RGBA8) ? rt::kOutRgba8 : 0u);
-    K.lanes = c->lanes;
-    K.walk = c->walk;
-    K.walk_leaf_den = c->walk_leaf_den;
     // a counts render: pixel p's last index is sample_base + total_p - 1, and total_p <= total
     K.max_index = halton_max_index(c, p->sample_base, ca ? (uint32_t)total : p->spp);
+
+    // the box-cluster render kernel reads its waves' masks from the context's table
+    // (the counts kernel keeps its own prologue); a fill goes before ev0
+    rt::WaveGrid wg{};
+    const bool masks = !ca && rt::wave_mask_grid(K, p->bounces, c->scene_mem, 0, &wg);
+    if (masks && (st = ensure_wave_masks(c, &K, wg, stream)) != RT_OK) return st;
 
     if (keep_sum && !p->accumulate) c->sum_valid = false;  // being overwritten
     if ((st = timed_launch(c, stream, ca ? "path_counts" : "path_trace", &c->launch, [&](rt::LaunchInfo* info) {
@@ -550,6 +660,7 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
                        : rt::launch_path_trace(K, p->bounces, c->scene_mem, stream, info);
          })) != RT_OK)
         return st;
+    if (masks && (st = note_mask_reader(c, stream)) != RT_OK) return st;
     if (sums) {  // the kernel (re)wrote the running sums
         c->sum_valid = true;
         c->sum_row_start = start;
@@ -1204,6 +1315,7 @@ int rt_update_scene(rt_ctx* c, const rt_scene_desc* d, uint32_t flags) {
     c->broken = "rt_update_scene in progress";
     c->sum_valid = false;
     c->scene = std::move(next);
+    ++c->scene_epoch;  // the per-wave masks of the old tables no longer hold (ensure_wave_masks)
     const auto t_up = clk::now();
     if ((e = upload_scene(c)) != hipSuccess) return broken(RT_ERR_OUT_OF_MEMORY, std::string("scene upload: ") + hipGetErrorString(e));
     st.upload_ms = ms_since(t_up);
@@ -1502,6 +1614,49 @@ int rt_debug_halton_table_device(const rt_ctx* c, float* table, uint32_t capacit
     const hipError_t e =
         hipMemcpy(table, c->d_halton_tab.as<void>(), sizeof(float) * rt::kHaltonTabLdsFloats, hipMemcpyDeviceToHost);
     return e == hipSuccess ? RT_OK : RT_ERR_LAUNCH;
+}
+
+int rt_debug_wave_masks(rt_ctx* c, const rt_render_params* p, uint32_t lanes, rt_wave_mask* masks, uint32_t capacity,
+                        uint32_t* waves_x, uint32_t* waves_y, uint64_t* fills) {
+    static_assert(sizeof(rt_wave_mask) == 32 && sizeof(rt::WaveMask) == 16, "rt_wave_mask / WaveMask layout");
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    if (!p || !waves_x || !waves_y || (!masks && capacity))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_debug_wave_masks: null argument");
+    if (lanes != 0 && lanes != 1 && lanes != 4 && lanes != 16)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_debug_wave_masks: lanes_per_pixel must be 0, 1, 4 or 16");
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
+    if (p->bounces > RT_MAX_BOUNCES) return fail(c, RT_ERR_INVALID_ARG, "bounces > 4");
+    uint32_t start, step, count;
+    if (!resolve_rows(c, p->row_start, p->row_step, p->row_count, &start, &step, &count))
+        return fail(c, RT_ERR_INVALID_ARG, "row partition outside the frame");
+    DeviceGuard g(c->device);
+    rt::KParams K;
+    set_scene(&K, c);
+    set_launch(&K, c, p, start, step, count);
+    K.max_index = halton_max_index(c, p->sample_base, p->spp);
+    *waves_x = *waves_y = 0;
+    if (fills) *fills = c->mask_fills;
+    rt::WaveGrid wg{};
+    if (!rt::wave_mask_grid(K, p->bounces, c->scene_mem, lanes, &wg)) return RT_OK;
+    int st;
+    if ((st = ensure_wave_masks(c, &K, wg, c->stream)) != RT_OK) return st;
+    if (fills) *fills = c->mask_fills;
+    const uint32_t n = wg.waves_x * wg.waves_y;
+    std::vector<rt::WaveMask> host(n);
+    hipError_t e = hipMemcpyAsync(host.data(), c->d_wave_masks.as<void>(), (size_t)n * sizeof(rt::WaveMask),
+                                  hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "rt_debug_wave_masks: read-back", e);
+    *waves_x = wg.waves_x;
+    *waves_y = wg.waves_y;
+    wave_rects(wg, start, step, masks, capacity);
+    for (uint32_t w = 0; w < n && w < capacity; ++w) {
+        masks[w].cam_mask = host[w].cam_mask;
+        masks[w].shd_mask = host[w].shd_mask;
+        masks[w].shd_cskip = host[w].shd_cskip;
+        masks[w].shd_available = host[w].shd_avail;
+    }
+    return RT_OK;
 }
 
 int rt_last_launch(const rt_ctx* c, rt_launch_info* info) {

@@ -390,6 +390,23 @@ int rt_debug_shadow_candidates(const rt_scene_desc* d, int32_t x0, int32_t x1, i
     return RT_OK;
 }
 
+int rt_debug_wave_rects(int32_t width, int32_t height, uint32_t row_start, uint32_t row_step, uint32_t row_count,
+                        uint32_t lanes, rt_wave_mask* masks, uint32_t capacity, uint32_t* waves_x, uint32_t* waves_y) {
+    static_assert(sizeof(rt_wave_mask) == 32, "rt_wave_mask layout");
+    if (width < 1 || height < 1 || !waves_x || !waves_y || (!masks && capacity))
+        return fail(nullptr, RT_ERR_INVALID_ARG, "rt_debug_wave_rects: empty frame or null argument");
+    if (lanes != 1 && lanes != 4 && lanes != 16)
+        return fail(nullptr, RT_ERR_INVALID_ARG, "rt_debug_wave_rects: lanes_per_pixel must be 1, 4 or 16");
+    uint32_t start, step, count;
+    if (!resolve_rows((uint32_t)height, row_start, row_step, row_count, &start, &step, &count))
+        return fail(nullptr, RT_ERR_INVALID_ARG, "row partition outside the frame");
+    const rt::WaveGrid g = rt::clu_wave_grid((uint32_t)width, count, step, lanes);
+    *waves_x = g.waves_x;
+    *waves_y = g.waves_y;
+    wave_rects(g, start, step, masks, capacity);
+    return RT_OK;
+}
+
 int rt_debug_cluster_kinds(const rt_scene_desc* d, uint32_t* flags, uint32_t capacity, uint32_t* n_clusters) {
     if (!desc_ok(d) || !n_clusters || (!flags && capacity)) return fail(nullptr, RT_ERR_INVALID_ARG, "null argument");
     rt::CompiledScene s;

@@ -96,6 +96,34 @@ inline TileLayout tile_layout(uint32_t W, uint32_t H, uint32_t N, uint32_t rank,
     return L;
 }
 
+// The pixel rectangles of the waves of g over the rows row_start + j * row_step
+// (rt_debug_wave_rects, rt_debug_wave_masks): wave w = wy * waves_x + wx covers
+// columns wx * wave_w .. + wave_w - 1 and partition rows wy * wave_h .. +
+// wave_h - 1, which is what wave_masks_kernel builds its beam from.
+inline void wave_rects(const rt::WaveGrid& g, uint32_t row_start, uint32_t row_step, rt_wave_mask* out,
+                       uint32_t capacity) {
+    const uint32_t n = g.waves_x * g.waves_y;
+    for (uint32_t w = 0; w < n && w < capacity; ++w) {
+        const uint32_t wx0 = (w % g.waves_x) * g.wave_w, wj0 = (w / g.waves_x) * g.wave_h;
+        out[w].x0 = (int32_t)wx0;
+        out[w].x1 = (int32_t)(wx0 + g.wave_w - 1u);
+        out[w].y0 = (int32_t)(row_start + wj0 * row_step);
+        out[w].y1 = (int32_t)(row_start + (wj0 + g.wave_h - 1u) * row_step);
+    }
+}
+
+// Resolves the defaults of a row partition (0: step 1, every row from
+// row_start on) and validates it against a frame of H rows.
+inline bool resolve_rows(uint32_t H, uint32_t row_start, uint32_t row_step, uint32_t row_count, uint32_t* start,
+                         uint32_t* step, uint32_t* count) {
+    *start = row_start;
+    *step = row_step ? row_step : 1u;
+    if (*start >= H) return false;
+    const uint32_t avail = (H - 1u - *start) / *step + 1u;
+    *count = row_count ? row_count : avail;
+    return *count <= avail;
+}
+
 // rt_plan_params (rt_plan_samples and rt_plan_samples_host): null when every
 // field is in its range, else what is wrong.  `flags_ok`: the flag bits the
 // entry point accepts.

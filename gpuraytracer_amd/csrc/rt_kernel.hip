@@ -637,60 +637,6 @@ void path_trace_kernel(KParams P) {
         x = bx * (WR * kWX) + (wave % WR) * kWX + (pix % kWX);
         j = by * (WC * kWY) + (wave / WR) * kWY + (pix / kWX);
     };
-    if constexpr (RT_CAM_CAND && GEO == kGeoPairClu) {
-        // The pairs this wave's camera rays can hit (rt_beam.hpp, DESIGN.md
-        // §3.16), once per wave: the footprint is the wave's pixel rectangle
-        // from the tile geometry (the same for the whole launch), lane k tests
-        // pair k (nP <= 31 with box clusters) and the ballot is the mask.
-        // Before the early return below: a ballot only sees active lanes.
-        if (sv.nP - 1u < 32u) {  // wave-uniform: 1..32 pairs, else cluster_query as before
-            const uint32_t wave = wave_uniform(threadIdx.x >> 6);
-            const uint32_t wx0 = bx * (WR * kWX) + (wave % WR) * kWX;
-            const uint32_t wj0 = by * (WC * kWY) + (wave / WR) * kWY;
-            const float y0 = (float)(P.row_start + wj0 * P.row_step);
-            const float y1 = (float)(P.row_start + (wj0 + kWY - 1u) * P.row_step);
-            const Beam beam = make_beam(ld_f3(P.cam_pos), ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), P.halfW,
-                                        P.halfH, (float)P.W, (float)P.H, (float)wx0, (float)(wx0 + kWX - 1u), y0, y1);
-            const uint32_t k = threadIdx.x & 63u;
-            const uint32_t kc = min(k, sv.nP - 1u);  // lanes past the last pair re-test it (discarded)
-            const bool keep = !beam_excludes_pair(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * kc));
-            sv.cam_mask = wave_uniform((uint32_t)__builtin_amdgcn_ballot_w64(k < sv.nP && keep));
-            sv.cam_avail = true;
-            if constexpr (RT_SHD_CAND) {
-                // The pairs that can occlude this wave's bounce-0 shadow rays
-                // (rt_shaft.hpp), for a wave whose camera
-                // mask holds ONE pair (nine tiles in ten; the beam is then dead
-                // before the target tests: no spill): lane k and lane k + 32
-                // test target pair k against the shafts of its triangle A and
-                // its triangle B; the mask is the union.  A light's triangle
-                // ends the path: it casts no shadow ray.  More source pairs:
-                // nothing is decided, the generic query runs.
-                const uint32_t tb = k >> 5, kt = min(k & 31u, sv.nP - 1u);
-                bool occ = false, bad = (sv.cam_mask & (sv.cam_mask - 1u)) != 0u;
-                if (sv.cam_mask != 0u && !bad) {  // wave-uniform
-                    const uint32_t sp = (uint32_t)__builtin_ctz(sv.cam_mask);
-                    const float4 s0 = P.tri_shade[4 * (2u * sp + tb)];
-                    if (s0.w == 0.0f) {
-                        const ShaftLight lq = shaft_light(ld_f3(P.light_center));
-                        const ShaftSrc src = shaft_source(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * sp),
-                                                          (int)tb, f3{s0.x, s0.y, s0.z}, lq);
-                        bad = !src.ok;
-                        occ = !shaft_excludes_pair(src, lq, reinterpret_cast<const float*>(sv.pair + kPairF4 * kt));
-                    }
-                }
-                const unsigned long long ob = __builtin_amdgcn_ballot_w64((k & 31u) < sv.nP && occ);
-                sv.shd_mask = wave_uniform((uint32_t)ob | (uint32_t)(ob >> 32));
-                sv.shd_avail = __builtin_amdgcn_ballot_w64(bad) == 0ull && sv.nC <= 32u;
-                // clusters none of whose faces is in the mask (record word 22: all its pairs)
-                if (sv.nC != 0u) {
-                    const uint32_t kc2 = min(k, sv.nC - 1u);
-                    const uint32_t all = __float_as_uint(reinterpret_cast<const float*>(sv.clu + kCluF4 * kc2)[22]);
-                    sv.shd_cskip = wave_uniform(
-                        (uint32_t)__builtin_amdgcn_ballot_w64(k < sv.nC && (all & sv.shd_mask) == 0u));
-                }
-            }
-        }
-    }
     // Per-lane constants (pixel coordinates, lane roles) are recomputed from an
     // opaque copy of threadIdx.x where they are used, and the seed is kept in
     // LDS: otherwise the compiler hoists them out of the sample loop and spills
@@ -729,6 +675,27 @@ void path_trace_kernel(KParams P) {
             lum_s[3 * slot] = lum.x;
             lum_s[3 * slot + 1] = lum.y;
             lum_s[3 * slot + 2] = lum.z;
+        }
+    }
+    if constexpr (RT_CAM_CAND && GEO == kGeoPairClu) {
+        // The pairs this wave's camera rays can hit and the pairs that can
+        // occlude its bounce-0 shadow rays: fixed by
+        // the scene, the camera and the wave's pixel rectangle, so they come
+        // from the context's table (wave_masks_kernel below),
+        // one entry per wave in wave row-major order, one scalar load.  Placed
+        // after the seed staging: loaded before it, the L = 4 and L = 16 forms
+        // at 3 and 4 bounces spill a VGPR inside the sample loop.
+        if (sv.nP - 1u < 32u) {  // wave-uniform: 1..32 pairs, else no table: cluster_query as before
+            const uint32_t wave = wave_uniform(threadIdx.x >> 6);
+            const uint32_t wx = bx * WR + wave % WR, wy = by * WC + wave / WR;
+            const uint4 m = P.wave_masks[wave_uniform(wy * (gridDim.x * WR) + wx)];
+            sv.cam_mask = wave_uniform(m.x);
+            sv.cam_avail = true;
+            if constexpr (RT_SHD_CAND) {
+                sv.shd_mask = wave_uniform(m.y);
+                sv.shd_cskip = wave_uniform(m.z);
+                sv.shd_avail = wave_uniform(m.w) != 0u;
+            }
         }
     }
     const f3 cu = ld_f3(P.cam_u), cv = ld_f3(P.cam_v), cw = ld_f3(P.cam_w);
@@ -1049,11 +1016,11 @@ hipError_t launch_tl(const KParams& P, size_t lds_bytes, hipStream_t stream) {
     // for whole frames, one row of 64/L pixels when the rows are interleaved
     // (row_step > 1), which keeps a wave's camera rays adjacent in the image
     // (N = 8 share: 10,822 -> 11,211 Msamples/s)
-    if (L > 1) Q.wave_w = (P.row_step > 1) ? 64u / L : (L == 4 ? 4u : 2u);
-    constexpr uint32_t WR = waves_per_row(GEO), WC = waves_per_col(GEO);
-    const uint32_t WX = (L == 1) ? 8u : Q.wave_w;
-    const uint32_t TX = WR * WX, TY = WC * ((64u / L) / WX);
-    const dim3 grid((P.W + TX - 1) / TX, (P.row_count + TY - 1) / TY);
+    const WaveGrid g = wave_grid((uint32_t)P.W, P.row_count, P.row_step, (uint32_t)L, waves_per_row(GEO), waves_per_col(GEO));
+    if (L > 1) Q.wave_w = g.wave_w;
+    const dim3 grid(g.grid_x, g.grid_y);
+    // the box-cluster kernel reads its waves' masks from the context's table
+    if (RT_CAM_CAND && GEO == kGeoPairClu && P.nP - 1u < 32u && !P.wave_masks) return hipErrorInvalidValue;
     if (GEO == kGeoSphLds) {
         const hipError_t e = allow_lds((const void*)path_trace_kernel<B, GEO, SPH, SMALL, L>, lds_bytes);
         if (e != hipSuccess) return e;
@@ -1238,6 +1205,17 @@ hipError_t launch_path_trace(const KParams& P, uint32_t bounces, SceneMem mem,
     return e;
 }
 
+bool wave_mask_grid(const KParams& P, uint32_t bounces, SceneMem mem, uint32_t lanes_override, WaveGrid* g) {
+    if (!RT_CAM_CAND || P.nP - 1u >= 32u) return false;
+    if (choose_kernel(tables_of(P), P.sph_lds != nullptr, bounces, mem, P.walk).layout != kGeoPairClu) return false;
+    KParams Q = P;
+    if (lanes_override) Q.lanes = lanes_override;
+    // launch_h and launch_t: lanes per pixel above 1 only with fixed-digit indices
+    const int L = P.max_index < kSmallIndexMax ? lanes_per_pixel(Q, kGeoPairClu) : 1;
+    *g = clu_wave_grid((uint32_t)P.W, P.row_count, P.row_step, (uint32_t)(L == 16 || L == 4 ? L : 1));
+    return true;
+}
+
 // the render with per-pixel sample counts: after every kernel and launcher above
 #include "rt_counts.hpp"
 // path-traced radiance along the caller's own rays: after the counts kernels
@@ -1303,6 +1281,73 @@ hipError_t launch_fill_seeds(uint32_t* seeds, uint64_t key, uint64_t n, hipStrea
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(fill_seeds_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, seeds,
                        key, n);
+    return hipGetLastError();
+}
+
+// The mask table of one launch geometry: wave w of this
+// kernel decides entry w = wy * waves_x + wx, the masks of the render wave
+// whose pixels are columns wx * wave_w .. and partition rows wy * wave_h ..
+// The tests are rt_beam.hpp's and rt_shaft.hpp's, in the lane layout the
+// render kernel's prologue had: lane k tests pair k against the wave's beam
+// and the ballot is the camera mask; lane k and lane k + 32 test target pair k
+// against the shafts of triangle A and triangle B of a source pair, for EVERY
+// pair of the camera mask in turn (wave-uniform loop), and the occluder mask is
+// the union.  A light's triangle ends the path: it casts no shadow ray.  One
+// undecidable source (a grazing or crossing plane): nothing is decided for the
+// wave, the generic query runs.  The records come from global memory.
+// A template, instantiated by the launcher below, last in this file: the code
+// object keeps the order of the kernels before it (tools/isa_diff.sh).
+template <bool MULTI>
+__global__ __launch_bounds__(kBlockThreads) void wave_masks_kernel(KParams P, uint4* table, uint32_t waves_x,
+                                                                   uint32_t n_waves, uint32_t kWX, uint32_t kWY) {
+    const uint32_t w = wave_uniform(blockIdx.x * (kBlockThreads / 64u) + (threadIdx.x >> 6));
+    if (w >= n_waves) return;  // wave-uniform
+    const uint32_t nP = P.nP, nC = P.nC;  // 1..32 pairs (wave_mask_grid)
+    const float* pair = reinterpret_cast<const float*>(P.pair_isect);
+    const uint32_t wx0 = (w % waves_x) * kWX, wj0 = (w / waves_x) * kWY;
+    const float y0 = (float)(P.row_start + wj0 * P.row_step);
+    const float y1 = (float)(P.row_start + (wj0 + kWY - 1u) * P.row_step);
+    const Beam beam = make_beam(ld_f3(P.cam_pos), ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), P.halfW, P.halfH,
+                                (float)P.W, (float)P.H, (float)wx0, (float)(wx0 + kWX - 1u), y0, y1);
+    const uint32_t k = threadIdx.x & 63u;
+    const uint32_t kc = min(k, nP - 1u);  // lanes past the last pair re-test it (discarded)
+    const bool keep = !beam_excludes_pair(beam, pair + 4u * kPairF4 * kc);
+    const uint32_t cam_mask = wave_uniform((uint32_t)__builtin_amdgcn_ballot_w64(k < nP && keep));
+    uint32_t shd_mask = 0u, shd_cskip = 0u;
+    bool shd_avail = false;
+    if constexpr (RT_SHD_CAND) {
+        const uint32_t tb = k >> 5, kt = min(k & 31u, nP - 1u);
+        const ShaftLight lq = shaft_light(ld_f3(P.light_center));
+        bool undecided = !MULTI && (cam_mask & (cam_mask - 1u)) != 0u;
+        for (uint32_t m = undecided ? 0u : cam_mask; m != 0u; m &= m - 1u) {  // wave-uniform
+            const uint32_t sp = (uint32_t)__builtin_ctz(m);
+            const float4 s0 = P.tri_shade[4 * (2u * sp + tb)];
+            bool occ = false, bad = false;
+            if (s0.w == 0.0f) {
+                const ShaftSrc src = shaft_source(beam, pair + 4u * kPairF4 * sp, (int)tb, f3{s0.x, s0.y, s0.z}, lq);
+                bad = !src.ok;
+                occ = !shaft_excludes_pair(src, lq, pair + 4u * kPairF4 * kt);
+            }
+            const unsigned long long ob = __builtin_amdgcn_ballot_w64((k & 31u) < nP && occ);
+            shd_mask |= wave_uniform((uint32_t)ob | (uint32_t)(ob >> 32));
+            undecided = undecided || __builtin_amdgcn_ballot_w64(bad) != 0ull;
+        }
+        shd_avail = !undecided && nC <= 32u;
+        // clusters none of whose faces is in the mask (record word 22: all its pairs)
+        if (nC != 0u) {
+            const uint32_t kc2 = min(k, nC - 1u);
+            const uint32_t all = __float_as_uint(reinterpret_cast<const float*>(P.clusters + kCluF4 * kc2)[22]);
+            shd_cskip = wave_uniform((uint32_t)__builtin_amdgcn_ballot_w64(k < nC && (all & shd_mask) == 0u));
+        }
+    }
+    if (k == 0u) table[w] = make_uint4(cam_mask, shd_mask, shd_cskip, shd_avail ? 1u : 0u);
+}
+
+hipError_t launch_wave_masks(const KParams& P, const WaveGrid& g, uint4* table, hipStream_t stream) {
+    const uint32_t n = g.waves_x * g.waves_y, per_block = kBlockThreads / 64u;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(wave_masks_kernel<RT_WAVE_MASK_MULTI != 0>, dim3((n + per_block - 1) / per_block), dim3(kBlockThreads), 0, stream, P, table,
+                       g.waves_x, n, g.wave_w, g.wave_h);
     return hipGetLastError();
 }
 

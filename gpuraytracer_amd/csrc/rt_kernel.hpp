@@ -146,7 +146,48 @@ struct KParams {
                               // TriShade s0.w != 0 (ids < 64; rt_scene.hpp light_mask)
     const float* halton_tab;  // box-cluster kernel: the context's Halton low-digit tables, kHaltonTabLdsFloats
                               // floats (launch_fill_halton_tables), copied into LDS when halton_tables_on
+    const uint4* wave_masks;  // box-cluster render kernel, 1..32 pairs: one WaveMask per wave of this launch's
+                              // geometry in wave row-major order (launch_wave_masks)
 };
+
+// ---- per-wave candidate masks (rt_kernel.hip wave_masks_kernel)
+// What the box-cluster render kernel knows about one wave before its first
+// sample, 16 B that the wave reads with one scalar load: the pairs its camera
+// rays can hit (rt_beam.hpp), the pairs that can occlude its bounce-0 shadow
+// rays (rt_shaft.hpp), the box clusters none of whose faces is among those, and
+// whether the occluder mask is decided.
+struct WaveMask {
+    uint32_t cam_mask, shd_mask, shd_cskip, shd_avail;
+};
+static_assert(sizeof(WaveMask) == sizeof(uint4), "one dwordx4 load per wave");
+// The occluder mask of a wave with SEVERAL camera pairs is the union over all of
+// them; 0: decided only for one camera pair, as the render kernel's own
+// prologue did before the table (the A/B switch of profiles/r22/ab_results.md)
+#ifndef RT_WAVE_MASK_MULTI
+#define RT_WAVE_MASK_MULTI 1
+#endif
+// THE wave geometry of a lockstep launch at L lanes per pixel over W columns and
+// row_count rows of the row partition: a wave is wave_w x wave_h pixels (8x8 at
+// L = 1; L > 1: 4x4 / 2x2 for whole frames, one row of 64/L pixels when the rows
+// are interleaved), a workgroup WR x WC waves, and the grid rounds up to whole
+// workgroups: waves_x x waves_y waves, some of them past the frame's edge.
+// Wave (wx, wy) covers columns wx * wave_w .. + wave_w - 1 and partition rows
+// wy * wave_h .. + wave_h - 1.  launch_tl and the mask table share this one
+// definition.
+struct WaveGrid {
+    uint32_t L, wave_w, wave_h, grid_x, grid_y, waves_x, waves_y;
+};
+constexpr WaveGrid wave_grid(uint32_t W, uint32_t row_count, uint32_t row_step, uint32_t L, uint32_t WR,
+                             uint32_t WC) {
+    const uint32_t ww = L == 1 ? 8u : (row_step > 1 ? 64u / L : (L == 4 ? 4u : 2u));
+    const uint32_t wh = (64u / L) / ww;
+    const uint32_t gx = (W + WR * ww - 1) / (WR * ww), gy = (row_count + WC * wh - 1) / (WC * wh);
+    return WaveGrid{L, ww, wh, gx, gy, gx * WR, gy * WC};
+}
+// The box-cluster kernel's workgroup: 2 x 2 waves (rt_kernel.hip block_threads).
+constexpr WaveGrid clu_wave_grid(uint32_t W, uint32_t row_count, uint32_t row_step, uint32_t L) {
+    return wave_grid(W, row_count, row_step, L, 2u, 2u);
+}
 
 size_t kernel_lds_bytes(uint32_t n_tri, uint32_t n_pairs, uint32_t n_sph, uint32_t n_nodes);
 
@@ -232,6 +273,15 @@ enum class SceneMem { kAuto = 0, kLdsSingle = 1, kSmem = 2, kPairSorted = 3, kPa
 hipError_t launch_path_trace(const KParams& P, uint32_t bounces, SceneMem mem, hipStream_t stream,
                              LaunchInfo* info);
 KernelChoice choose_kernel(const SceneTables& t, bool sph_compact, uint32_t bounces, SceneMem mem, uint32_t walk);
+// Whether launch_path_trace(P, bounces, mem) reads P.wave_masks (the box-cluster
+// kernel on a scene of 1..32 pairs), and then *g: the wave geometry it launches
+// with, lanes_override = 0, or with that many lanes per pixel instead of P.lanes.
+// The masks depend on P's camera, light centre, tables, W, H, row partition and
+// on *g, on nothing else of P.
+bool wave_mask_grid(const KParams& P, uint32_t bounces, SceneMem mem, uint32_t lanes_override, WaveGrid* g);
+// Fills table[wy * g.waves_x + wx] for every wave of g: one launch of
+// wave_masks_kernel on `stream`.
+hipError_t launch_wave_masks(const KParams& P, const WaveGrid& g, uint4* table, hipStream_t stream);
 // The render with one sample count per pixel (rt_counts.hpp; include/rtpt.h
 // rt_render_counts): pixel p draws min(counts[p], P.spp) samples after the
 // P.sum[p].w samples its sum holds (P.accumulate), `totals` (or null) receives

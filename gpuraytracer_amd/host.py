@@ -22,7 +22,7 @@ from ._native import (MATH_FNS, RT_MATH_DEVICE, RT_MATH_HOST, RT_MATH_VALUES_MAX
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, RT_UPDATE_REBUILD, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
                       PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, RenderParamsC,
-                      RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, UpdateStats, float3,
+                      RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, UpdateStats, WaveMask, float3,
                       lib)
 
 DEFAULT_SEED_KEY = 0x5EED00000000
@@ -51,6 +51,33 @@ def tonemap_rgba8(rgba32f: np.ndarray) -> np.ndarray:
     lib.rt_tonemap_rgba8(a.ctypes.data_as(ctypes.c_void_p), n,
                          out.ctypes.data_as(ctypes.c_void_p))
     return out
+
+
+WAVE_MASK_DTYPE = np.dtype([(n, np.uint32) for n in ("cam_mask", "shd_mask", "shd_cskip", "shd_available")] +
+                           [(n, np.int32) for n in ("x0", "x1", "y0", "y1")])
+assert WAVE_MASK_DTYPE.itemsize == ctypes.sizeof(WaveMask)
+
+
+def _wave_records(call) -> np.ndarray:
+    """The records of rt_debug_wave_rects / rt_debug_wave_masks as a
+    (waves_y, waves_x) array: a first call for the counts, a second for the
+    records."""
+    wx, wy = ctypes.c_uint32(), ctypes.c_uint32()
+    call(None, 0, wx, wy)
+    out = np.zeros((wy.value, wx.value), dtype=WAVE_MASK_DTYPE)
+    if out.size:
+        call(out.ctypes.data_as(ctypes.c_void_p), out.size, wx, wy)
+    return out
+
+
+def wave_rects(width: int, height: int, lanes: int, row_start: int = 0, row_step: int = 1,
+               row_count: int = 0) -> np.ndarray:
+    """rt_debug_wave_rects (host only): the pixel rectangles (x0, x1, y0, y1,
+    closed; image rows y0, y0 + row_step, .., y1) of the waves of a lockstep
+    launch at ``lanes`` lanes per pixel, as a (waves_y, waves_x) record array
+    whose mask fields are 0."""
+    return _wave_records(lambda p, cap, wx, wy: _check(lib.rt_debug_wave_rects(
+        width, height, row_start, row_step, row_count, lanes, p, cap, ctypes.byref(wx), ctypes.byref(wy))))
 
 
 def _math_fn(fn: str, dim: int, where: str) -> tuple[int, int]:
@@ -1128,6 +1155,20 @@ class Renderer:
         info = LaunchInfo()
         _check(lib.rt_last_launch(self._ctx, ctypes.byref(info)), self._ctx)
         return info.as_dict()
+
+    def wave_masks(self, params: RenderParams | None = None, lanes: int = 0):
+        """rt_debug_wave_masks: the per-wave candidate masks the render of
+        ``params`` reads (with ``lanes`` lanes per pixel instead of the
+        context's when not 0), read back from the context's table, as a
+        (waves_y, waves_x) record array of WAVE_MASK_DTYPE -- empty when that
+        launch reads no table -- and how often the context has filled its
+        table so far."""
+        p = (params or RenderParams()).c()
+        fills = ctypes.c_uint64()
+        rec = _wave_records(lambda ptr, cap, wx, wy: _check(lib.rt_debug_wave_masks(
+            self._ctx, ctypes.byref(p), lanes, ptr, cap, ctypes.byref(wx), ctypes.byref(wy), ctypes.byref(fills)),
+            self._ctx))
+        return rec, int(fills.value)
 
     def build_info(self) -> dict:
         """rt_build_info: which triangle-BVH build ran (0 none, 1 host SAH, 2 GPU

@@ -952,6 +952,43 @@ int rt_debug_halton_table(float* table, uint32_t capacity, uint32_t* n_floats, u
  * has the tables on); capacity >= *n_floats of rt_debug_halton_table. */
 int rt_debug_halton_table_device(const rt_ctx* ctx, float* table, uint32_t capacity);
 
+/* Debug: the per-wave candidate masks of a render launch.
+ * The box-cluster render kernel (a triangle-only scene of 1..32 pairs with box
+ * clusters) reads, per wave, the pairs its camera rays can hit and the pairs
+ * that can occlude its bounce-0 shadow rays from a table the context fills
+ * once per (scene, camera, row partition, wave geometry) and then reuses.
+ * One record per wave of the launch, in wave row-major order: */
+typedef struct rt_wave_mask {
+    uint32_t cam_mask;      /* bit k: the camera rays can hit pair k (triangles 2k, 2k+1) */
+    uint32_t shd_mask;      /* bit k: pair k can occlude a bounce-0 shadow ray */
+    uint32_t shd_cskip;     /* bit c: box cluster c holds no pair of shd_mask */
+    uint32_t shd_available; /* 0: shd_mask is undecided (the generic query runs) */
+    int32_t x0, x1, y0, y1; /* the wave's pixel rectangle, closed, image rows y0, y0 + row_step, .., y1; it is
+                               what the tests ran on and may reach past the frame (the launch rounds up to
+                               whole workgroups) */
+} rt_wave_mask;
+/* rt_debug_wave_rects (host-only, no context, no device): the wave rectangles
+ * of a lockstep launch over `width` columns and the row partition
+ * (row_start, row_step, row_count; 0 resolves as for rt_render) of a frame of
+ * `height` rows at lanes_per_pixel 1, 4 or 16: only x0..y1 of each record are
+ * written.  *waves_x, *waves_y: the launch's waves per row and rows of waves;
+ * masks has room for capacity records and may be null when capacity is 0.
+ * Every pixel of the partition's rows lies in exactly one rectangle.
+ * rt_debug_wave_masks: the records of the launch rt_render(ctx, params) would
+ * make -- with lanes_per_pixel 1, 4 or 16 instead of the context's when it is
+ * not 0 -- read back from the context's table, which is filled for that launch
+ * first unless it already holds it; *fills (may be null): how often this
+ * context has filled its table so far.  *waves_x = *waves_y = 0 and RT_OK when
+ * that launch reads no table (another kernel layout, more than 32 pairs).
+ * Synchronises the context's stream.
+ * Added without a change of RTPT_ABI_VERSION: detect them by the presence of
+ * the symbol rt_debug_wave_masks (dlsym). */
+int rt_debug_wave_rects(int32_t width, int32_t height, uint32_t row_start, uint32_t row_step, uint32_t row_count,
+                        uint32_t lanes_per_pixel, rt_wave_mask* masks, uint32_t capacity, uint32_t* waves_x,
+                        uint32_t* waves_y);
+int rt_debug_wave_masks(rt_ctx* ctx, const rt_render_params* params, uint32_t lanes_per_pixel, rt_wave_mask* masks,
+                        uint32_t capacity, uint32_t* waves_x, uint32_t* waves_y, uint64_t* fills);
+
 /* Debug (host-only): the light mask the box-cluster kernel tests instead of
  * loading a hit triangle's light flag: bit id of *mask is set
  * when triangle id is a light (scenes of at most 64 triangles, else 0).
