@@ -19,7 +19,7 @@ HOSTFLAGS := $(COMMON) -D__HIP_PLATFORM_AMD__ -isystem /opt/rocm/include $(EXTRA
 DEV_OBJS := rt_kernel.o rt_rays.o rt_aov.o rt_denoise.o rt_adaptive.o rt_mis.o rt_lbvh.o rt_gsah.o rt_refit.o rt_mathcheck.o
 HOST_OBJS := rt_api.o rt_api_host.o rt_scene.o rt_image.o
 OBJS := $(addprefix $(BLD)/,$(DEV_OBJS) $(HOST_OBJS))
-HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp $(SRC)/rt_plan.hpp
+HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp $(SRC)/rt_plan.hpp $(SRC)/rt_wavemask.hpp
 
 LIB ?= $(PKG)/librtpt.so
 # Hash of every source the library is built from (gpuraytracer_amd/srchash.py),

@@ -144,16 +144,7 @@ hipError_t launch_plan(const PlanParams& P, hipStream_t stream, LaunchInfo* info
     const dim3 grid2((uint32_t)(blocks < kPlanGroups ? blocks : kPlanGroups));
     hipLaunchKernelGGL(plan_counts_kernel, grid2, dim3(kThreads), 0, stream, P);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (info) {
-        snprintf(info->kernel, sizeof(info->kernel), "rt::plan_counts_kernel");
-        info->lanes = 1;
-        info->tables = 0;
-        info->small = 0;
-        info->threads = kThreads;
-        info->grid_x = grid2.x;
-        info->grid_y = 1;
-        info->lds = 0;
-    }
+    if (info) fill_launch_info(*info, 1, false, false, kThreads, grid2, 0, "rt::plan_counts_kernel");
     return hipSuccess;
 }
 

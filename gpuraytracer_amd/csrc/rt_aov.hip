@@ -32,6 +32,7 @@
 #include "rt_beam.hpp"
 #include "rt_pixel.hpp"
 #include "rt_trace.hpp"
+#include "rt_wavemask.hpp"
 
 namespace rt {
 namespace {
@@ -70,10 +71,8 @@ __global__ __launch_bounds__(kBlockThreads) void aov_kernel(AovParams P) {
             const uint32_t wave = wave_uniform(threadIdx.x >> 6);
             const uint32_t wx0 = bx * (WR * kWX) + (wave % WR) * kWX;
             const uint32_t wj0 = by * (WC * kWY) + (wave / WR) * kWY;
-            const float y0 = (float)(P.row_start + wj0 * P.row_step);
-            const float y1 = (float)(P.row_start + (wj0 + kWY - 1u) * P.row_step);
-            const Beam beam = make_beam(ld_f3(P.cam_pos), ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), P.halfW,
-                                        P.halfH, (float)P.W, (float)P.H, (float)wx0, (float)(wx0 + kWX - 1u), y0, y1);
+            const Beam beam = wave_beam(P, wx0, wj0, kWX, kWY);
+            // the camera mask of wave_masks_kernel, spelled out (tools/isa_diff.sh)
             const uint32_t k = threadIdx.x & 63u;
             const uint32_t kc = min(k, sv.nP - 1u);  // lanes past the last pair re-test it (discarded)
             const bool keep = !beam_excludes_pair(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * kc));
@@ -144,16 +143,8 @@ thread_local LaunchInfo g_last_aov;
 template <int GEO, bool SPH, bool SMALL>
 hipError_t launch_k(const AovParams& P, size_t lds_bytes, hipStream_t stream) {
     const dim3 grid((P.W + kTile - 1) / kTile, (P.row_count + kTile - 1) / kTile);
-    LaunchInfo& I = g_last_aov;
-    snprintf(I.kernel, sizeof(I.kernel), "rt::aov_kernel<%d, %s, %s>", GEO, SPH ? "true" : "false",
-             SMALL ? "true" : "false");
-    I.lanes = 1;
-    I.tables = halton_tables_on(GEO, SMALL, P.spp, 1u) ? 1u : 0u;
-    I.small = SMALL ? 1u : 0u;
-    I.threads = kBlockThreads;
-    I.grid_x = grid.x;
-    I.grid_y = grid.y;
-    I.lds = (uint32_t)lds_bytes;
+    fill_launch_info(g_last_aov, 1, halton_tables_on(GEO, SMALL, P.spp, 1u), SMALL, kBlockThreads, grid, lds_bytes,
+                     "rt::aov_kernel<%d, %s, %s>", GEO, SPH ? "true" : "false", SMALL ? "true" : "false");
     hipLaunchKernelGGL((aov_kernel<GEO, SPH, SMALL>), grid, dim3(kBlockThreads), lds_bytes, stream,
                        P);  // aov_lds_bytes of the layout
     return hipGetLastError();
@@ -166,31 +157,14 @@ hipError_t launch_h(const AovParams& P, hipStream_t stream) {
     return small ? launch_k<GEO, SPH, true>(P, lds, stream) : launch_k<GEO, SPH, false>(P, lds, stream);
 }
 
-// The box-cluster layout serves triangle-only scenes, the sphere layout sphere
-// scenes only (choose_kernel); every other layout has both sphere forms.
-template <int GEO>
-hipError_t launch_s(const AovParams& P, hipStream_t stream) {
-    if constexpr (GEO == kGeoPairClu) return launch_h<GEO, false>(P, stream);
-    else if constexpr (GEO == kGeoSphLds) return launch_h<GEO, true>(P, stream);
-    else return P.tab.nS > 0 ? launch_h<GEO, true>(P, stream) : launch_h<GEO, false>(P, stream);
-}
-
 }  // namespace
 
 hipError_t launch_aov(const AovParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info) {
     if (P.spp == 0 || P.W <= 0 || P.row_count == 0) return hipErrorInvalidValue;
     const KernelChoice kc = choose_kernel(P.tab, P.sph_compact != 0u, 3, mem, kWalkLockstep);
-    hipError_t e;
-    switch (ray_query_layout(kc.layout)) {
-        case kGeoTriLds: e = launch_s<kGeoTriLds>(P, stream); break;
-        case kGeoPairLds: e = launch_s<kGeoPairLds>(P, stream); break;
-        case kGeoTriGlobal: e = launch_s<kGeoTriGlobal>(P, stream); break;
-        case kGeoPairSmem: e = launch_s<kGeoPairSmem>(P, stream); break;
-        case kGeoTriBvh: e = launch_s<kGeoTriBvh>(P, stream); break;
-        case kGeoPairClu: e = launch_s<kGeoPairClu>(P, stream); break;
-        case kGeoSphLds: e = launch_s<kGeoSphLds>(P, stream); break;
-        default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = dispatch_layout(ray_query_layout(kc.layout), P.tab.nS, [&](auto g, auto sph) {
+        return launch_h<decltype(g)::value, decltype(sph)::value>(P, stream);
+    });
     if (info) *info = g_last_aov;
     return e;
 }

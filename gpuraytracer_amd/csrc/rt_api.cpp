@@ -242,6 +242,21 @@ int copy_down(rt_ctx* c, void* host, const void* dev, size_t bytes, hipStream_t 
     return e == hipSuccess ? RT_OK : hip_fail(c, RT_ERR_LAUNCH, what, e);
 }
 
+// The end of a call: a synchronous one waits for `stream`, and a failure there
+// is `status` with the caller's text; a launch that staged records in LDS then
+// reports what an RT_LDS_CHECK build found (rt_kernel.hip).
+int finish(rt_ctx* c, hipStream_t stream, bool sync, const char* what, bool staged = false,
+           int status = RT_ERR_LAUNCH) {
+    if (!sync) return RT_OK;
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(c, status, what, e);
+    uint32_t short_end = 0;
+    if (staged && rt::lds_check_result(&short_end) == hipSuccess && short_end)
+        return fail(c, RT_ERR_LAUNCH, "LDS overflow: staged records end at byte " + std::to_string(short_end) +
+                                          ", past the dispatch's dynamic LDS");
+    return RT_OK;
+}
+
 // Host data into an empty buffer of its size, waited for.
 hipError_t upload(DevBuf& b, const void* src, size_t bytes, hipStream_t s) {
     hipError_t e = b.resize_exact(bytes);
@@ -676,16 +691,7 @@ int render_impl(rt_ctx* c, const rt_render_params* p, void* out, bool out_is_dev
     if (want_out && !out_is_device &&
         (st = copy_down(c, out, kout, out_bytes, stream, "hipMemcpyAsync(out)")) != RT_OK)
         return st;
-    if (sync) {
-        hipError_t e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess)
-            return hip_fail(c, RT_ERR_LAUNCH, "path_trace execution", e);
-        uint32_t short_end = 0;  // RT_LDS_CHECK builds (rt_kernel.hip)
-        if (rt::lds_check_result(&short_end) == hipSuccess && short_end)
-            return fail(c, RT_ERR_LAUNCH, "LDS overflow: staged records end at byte " + std::to_string(short_end) +
-                                              ", past the dispatch's dynamic LDS");
-    }
-    return RT_OK;
+    return finish(c, stream, sync, "path_trace execution", /*staged*/ true);
 }
 
 // Rank 0's placement after the gather: tile row j of rank k -> frame row
@@ -755,11 +761,7 @@ int render_gather_impl(rt_ctx* c, const rt_render_params* p, void* frame, hipStr
     if ((e = hipEventRecord(c->ev_tiles, stream)) != hipSuccess)
         return hip_fail(c, RT_ERR_LAUNCH, "hipEventRecord(gather)", e);
     c->tiles_pending = true;
-    if (!dev) {
-        e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return hip_fail(c, RT_ERR_COMM, "render+gather execution", e);
-    }
-    return RT_OK;
+    return finish(c, stream, !dev, "render+gather execution", /*staged*/ false, RT_ERR_COMM);
 }
 
 // MIS sample table: the u of every strategy depends only on the sample index
@@ -862,9 +864,7 @@ int render_mis_impl(rt_ctx* c, const rt_mis_params* p, float* out, uint8_t* out8
         return st;
     if (out8 && !dev && (st = copy_down(c, out8, kout8, pixels * 4u, c->stream, "hipMemcpyAsync(out8)")) != RT_OK)
         return st;
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess)
-        return hip_fail(c, RT_ERR_LAUNCH, "mis execution", e);
-    return RT_OK;
+    return finish(c, c->stream, true, "mis execution");
 }
 
 // rt_trace_rays / rt_trace_rays_async: one launch of the query kernel
@@ -907,9 +907,7 @@ int trace_rays_impl(rt_ctx* c, const rt_ray* rays, uint64_t n, uint32_t flags, r
          })) != RT_OK)
         return st;
     if (!dev && (st = copy_down(c, hits, khits, hit_bytes, stream, "hipMemcpyAsync(hits)")) != RT_OK) return st;
-    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
-        return hip_fail(c, RT_ERR_LAUNCH, "ray_query execution", e);
-    return RT_OK;
+    return finish(c, stream, sync, "ray_query execution");
 }
 
 // rt_trace_paths / rt_trace_paths_async: one launch of the path-query kernel
@@ -979,15 +977,7 @@ int trace_paths_impl(rt_ctx* c, const rt_path_params* p, const rt_ray* rays, con
             (st = copy_down(c, first_hits, A.hits, hit_bytes, stream, "hipMemcpyAsync(first hits)")) != RT_OK)
             return st;
     }
-    if (sync) {
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess)
-            return hip_fail(c, RT_ERR_LAUNCH, "path_query execution", e);
-        uint32_t short_end = 0;  // RT_LDS_CHECK builds (rt_kernel.hip)
-        if (rt::lds_check_result(&short_end) == hipSuccess && short_end)
-            return fail(c, RT_ERR_LAUNCH, "LDS overflow: staged records end at byte " + std::to_string(short_end) +
-                                              ", past the dispatch's dynamic LDS");
-    }
-    return RT_OK;
+    return finish(c, stream, sync, "path_query execution", /*staged*/ true);
 }
 
 // rt_render_aov / rt_render_aov_async: one launch of the feature-buffer kernel
@@ -1052,10 +1042,7 @@ int render_aov_impl(rt_ctx* c, const rt_aov_params* p, const rt_aov_buffers* b, 
             if (host[k] && (st = copy_down(c, host[k], kbuf[k], bytes[k], stream, "hipMemcpyAsync(aov)")) != RT_OK)
                 return st;
     }
-    hipError_t e;
-    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
-        return hip_fail(c, RT_ERR_LAUNCH, "aov execution", e);
-    return RT_OK;
+    return finish(c, stream, sync, "aov execution");
 }
 
 // rt_denoise / rt_denoise_async: prepare, variance pre-filter and the a-trous
@@ -1118,9 +1105,7 @@ int denoise_impl(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buffers
                            [&](rt::LaunchInfo* info) { return rt::launch_denoise(K, stream, info); })) != RT_OK)
         return st;
     if (!dev && (st = copy_down(c, b->out, kout, bytes, stream, "hipMemcpyAsync(denoise out)")) != RT_OK) return st;
-    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
-        return hip_fail(c, RT_ERR_LAUNCH, "denoise execution", e);
-    return RT_OK;
+    return finish(c, stream, sync, "denoise execution");
 }
 
 // rt_plan_samples / rt_plan_samples_async: the planner's two kernels
@@ -1175,9 +1160,7 @@ int plan_impl(rt_ctx* c, const rt_plan_params* p, const float* first, const floa
                            stream);
         if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(plan stats)", e);
     }
-    if (sync && (e = hipStreamSynchronize(stream)) != hipSuccess)
-        return hip_fail(c, RT_ERR_LAUNCH, "plan execution", e);
-    return RT_OK;
+    return finish(c, stream, sync, "plan execution");
 }
 
 }  // namespace

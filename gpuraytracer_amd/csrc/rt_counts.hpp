@@ -43,33 +43,16 @@ struct row_sum_counts<L, L> {
 }  // namespace
 
 template <int B, int GEO, bool SPH, bool SMALL, int L>
-__global__ __launch_bounds__(block_threads(GEO),
-                             SPH ? kMinWavesPerEuSph
-                                 : (GEO == kGeoPairClu ? kMinWavesPerEuClu
-                                                       : (GEO == kGeoTriBvh ? RT_TRI_WAVES : kMinWavesPerEu)))
+__global__ __launch_bounds__(block_threads(GEO), lockstep_min_waves(GEO, SPH))
 void path_counts_kernel(KParams P, const uint32_t* __restrict__ counts, uint32_t* __restrict__ totals) {
     static_assert(L == 1 || L == 16, "the counts forms: one lane or one DPP row per pixel");
     constexpr uint32_t NT = block_threads(GEO), WR = waves_per_row(GEO), WC = waves_per_col(GEO);
     extern __shared__ float4 lds[];
     SceneView sv;
-    const SceneTables T = tables_of(P);
-    if (geo_staged(GEO)) {
-        const StagedF4<uint32_t> n = staged_f4(GEO, T.nT, T.nP, T.nC);
-        RT_LDS_GUARD(16 * (size_t)(n.rec + n.clu) + (GEO == kGeoPairClu ? 4 * (size_t)kHaltonTabFloats : 0));
-        stage_records<GEO, NT>(lds, T);
-        if (GEO == kGeoSphLds) {
-            __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
-            sv.xstash = sph_stash;
-        }
-        if (GEO == kGeoPairClu) {
-            const uint32_t tab0 = n.rec + n.clu;
-            const bool tab = halton_tables_on(GEO, SMALL, P.spp, L);  // the cap, not a pixel's count
-            sv.htab = tab ? reinterpret_cast<const float*>(lds + tab0) : nullptr;
-            if (tab) copy_halton_tables<NT>(reinterpret_cast<float*>(lds + tab0), P.halton_tab, threadIdx.x);
-        }
-        __syncthreads();
-    }
-    bind_scene<GEO, SPH>(sv, T, lds);
+    __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
+    // the Halton tables by the cap P.spp, not a pixel's count
+    RT_LDS_GUARD(staged_end(GEO, P, GEO == kGeoPairClu));
+    stage_scene<GEO, SPH, NT>(sv, P, lds, sph_stash, halton_tables_on(GEO, SMALL, P.spp, L));
 
     const uint32_t kWX = (L == 1) ? 8u : P.wave_w, kWY = (64u / L) / kWX;
     uint32_t bx, by;
@@ -87,10 +70,8 @@ void path_counts_kernel(KParams P, const uint32_t* __restrict__ counts, uint32_t
             const uint32_t wave = wave_uniform(threadIdx.x >> 6);
             const uint32_t wx0 = bx * (WR * kWX) + (wave % WR) * kWX;
             const uint32_t wj0 = by * (WC * kWY) + (wave / WR) * kWY;
-            const float y0 = (float)(P.row_start + wj0 * P.row_step);
-            const float y1 = (float)(P.row_start + (wj0 + kWY - 1u) * P.row_step);
-            const Beam beam = make_beam(ld_f3(P.cam_pos), ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), P.halfW,
-                                        P.halfH, (float)P.W, (float)P.H, (float)wx0, (float)(wx0 + kWX - 1u), y0, y1);
+            const Beam beam = wave_beam(P, wx0, wj0, kWX, kWY);
+            // the masks of wave_masks_kernel<false>, spelled out (tools/isa_diff.sh)
             const uint32_t k = threadIdx.x & 63u;
             const uint32_t kc = min(k, sv.nP - 1u);
             const bool keep = !beam_excludes_pair(beam, reinterpret_cast<const float*>(sv.pair + kPairF4 * kc));
@@ -259,36 +240,6 @@ hipError_t launch_counts_h(const KParams& P, const uint32_t* counts, uint32_t* t
                : launch_counts_tl<B, GEO, SPH, false, 1>(P, counts, totals, lds_bytes, stream);
 }
 
-// The sphere forms a layout can meet: the box-cluster layout serves
-// triangle-only scenes, the sphere kernel sphere scenes (choose_kernel).
-template <int B, int GEO>
-hipError_t launch_counts_g(const KParams& P, const uint32_t* counts, uint32_t* totals, size_t lds_bytes,
-                           hipStream_t stream) {
-    if constexpr (GEO == kGeoPairClu) {
-        return launch_counts_h<B, GEO, false>(P, counts, totals, lds_bytes, stream);
-    } else if constexpr (GEO == kGeoSphLds) {
-        return launch_counts_h<B, GEO, true>(P, counts, totals, lds_bytes, stream);
-    } else {
-        return P.nS > 0 ? launch_counts_h<B, GEO, true>(P, counts, totals, lds_bytes, stream)
-                        : launch_counts_h<B, GEO, false>(P, counts, totals, lds_bytes, stream);
-    }
-}
-
-template <int B>
-hipError_t launch_counts_b(const KParams& P, const uint32_t* counts, uint32_t* totals, int geo, size_t lds_bytes,
-                           hipStream_t stream) {
-    switch (geo) {
-        case kGeoPairLds: return launch_counts_g<B, kGeoPairLds>(P, counts, totals, lds_bytes, stream);
-        case kGeoPairClu: return launch_counts_g<B, kGeoPairClu>(P, counts, totals, lds_bytes, stream);
-        case kGeoSphLds: return launch_counts_g<B, kGeoSphLds>(P, counts, totals, lds_bytes, stream);
-        case kGeoPairSmem: return launch_counts_g<B, kGeoPairSmem>(P, counts, totals, lds_bytes, stream);
-        case kGeoTriBvh: return launch_counts_g<B, kGeoTriBvh>(P, counts, totals, lds_bytes, stream);
-        case kGeoTriLds: return launch_counts_g<B, kGeoTriLds>(P, counts, totals, lds_bytes, stream);
-        case kGeoTriGlobal: return launch_counts_g<B, kGeoTriGlobal>(P, counts, totals, lds_bytes, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_path_counts(const KParams& P, const uint32_t* counts, uint32_t* totals, uint32_t bounces,
@@ -298,15 +249,12 @@ hipError_t launch_path_counts(const KParams& P, const uint32_t* counts, uint32_t
     // the lockstep form of the context's layout, as a ray query takes it
     const int geo = ray_query_layout(choose_kernel(T, P.sph_lds != nullptr, bounces, mem, P.walk).layout);
     const size_t lds_bytes = staged_lds_bytes(geo, T.nT, T.nP, T.nC);
-    hipError_t e;
-    switch (bounces) {
-        case 0: e = launch_counts_b<0>(P, counts, totals, geo, lds_bytes, stream); break;
-        case 1: e = launch_counts_b<1>(P, counts, totals, geo, lds_bytes, stream); break;
-        case 2: e = launch_counts_b<2>(P, counts, totals, geo, lds_bytes, stream); break;
-        case 3: e = launch_counts_b<3>(P, counts, totals, geo, lds_bytes, stream); break;
-        case 4: e = launch_counts_b<4>(P, counts, totals, geo, lds_bytes, stream); break;
-        default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = dispatch_bounces(bounces, [&](auto b) {
+        return dispatch_layout(geo, P.nS, [&](auto g, auto sph) {
+            return launch_counts_h<decltype(b)::value, decltype(g)::value, decltype(sph)::value>(P, counts, totals,
+                                                                                                lds_bytes, stream);
+        });
+    });
     if (info) *info = g_last;
     return e;
 }

@@ -317,16 +317,9 @@ hipError_t launch_denoise(const DenoiseParams& P, hipStream_t stream, LaunchInfo
         else
             hipLaunchKernelGGL(denoise_atrous_kernel<false>, grid, block, 0, stream, A);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (A.last && info) {
-            snprintf(info->kernel, sizeof(info->kernel), "rt::denoise_atrous_kernel<%s>", lds ? "true" : "false");
-            info->lanes = 1;
-            info->tables = 0;
-            info->small = 0;
-            info->threads = kThreads;
-            info->grid_x = grid.x;
-            info->grid_y = grid.y;
-            info->lds = (uint32_t)lds;
-        }
+        if (A.last && info)
+            fill_launch_info(*info, 1, false, false, kThreads, grid, lds, "rt::denoise_atrous_kernel<%s>",
+                             lds ? "true" : "false");
     }
     return hipSuccess;
 }

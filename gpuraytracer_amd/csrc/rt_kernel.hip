@@ -34,6 +34,7 @@
 #include "rt_shaft.hpp"
 #include "rt_pixel.hpp"
 #include "rt_trace.hpp"
+#include "rt_wavemask.hpp"
 
 namespace rt {
 
@@ -63,6 +64,14 @@ static_assert(offsetof(hsa_kernel_dispatch_packet_t, group_segment_size) == 28, 
 #else
 #define RT_LDS_GUARD(end) ((void)0)
 #endif
+// The end a lockstep path kernel guards: its layout's records and clusters, and
+// the Halton tables where its launcher's request holds them (`tables`: the
+// render and the counts launchers request staged_lds_bytes, which has them for
+// every box-cluster launch; the path query's only when the launch copies them).
+__device__ __forceinline__ size_t staged_end(int geo, const KParams& P, bool tables) {
+    const StagedF4<size_t> n = staged_f4<size_t>(geo, P.nT, P.nP, P.nC);
+    return 16 * (n.rec + n.clu) + (tables ? 4 * (size_t)kHaltonTabLdsFloats : (size_t)0);
+}
 
 namespace {
 
@@ -591,38 +600,49 @@ constexpr uint32_t block_threads(int geo) { return geo == kGeoSphLds ? kSphBlock
 constexpr uint32_t waves_per_row(int geo) { return block_threads(geo) >= 128 ? 2u : 1u; }
 constexpr uint32_t waves_per_col(int geo) { return block_threads(geo) / 64u / waves_per_row(geo); }
 
-template <int B, int GEO, bool SPH, bool SMALL, int L = 1>
 #ifndef RT_TRI_WAVES
 #define RT_TRI_WAVES 8
 #endif
-__global__ __launch_bounds__(block_threads(GEO),
-                             SPH ? kMinWavesPerEuSph
-                                 : (GEO == kGeoPairClu ? kMinWavesPerEuClu
-                                                       : (GEO == kGeoTriBvh ? RT_TRI_WAVES : kMinWavesPerEu)))
-void path_trace_kernel(KParams P) {
-    constexpr uint32_t NT = block_threads(GEO), WR = waves_per_row(GEO), WC = waves_per_col(GEO);
-    extern __shared__ float4 lds[];
-    SceneView sv;
+// The waves per SIMD the lockstep path kernels (render, counts, path query) are
+// compiled for.
+constexpr int lockstep_min_waves(int geo, bool sph) {
+    return sph ? kMinWavesPerEuSph
+               : (geo == kGeoPairClu ? kMinWavesPerEuClu : (geo == kGeoTriBvh ? RT_TRI_WAVES : kMinWavesPerEu));
+}
+
+// THE staging prologue of the lockstep path kernels (render, counts, path
+// query), after the kernel's RT_LDS_GUARD: the workgroup's NT threads stage the
+// layout's intersection records once, then, for the box-cluster layout when
+// `tab` (the kernel's halton_tables_on), a copy of the context's Halton tables
+// (filled once, rt_create_ex: a copy, not a fill); one barrier; sv bound to the
+// scene (bind_scene).  sph_stash: the kernel's per-lane LDS stash of shade()
+// (the sphere kernel).
+template <int GEO, bool SPH, uint32_t NT>
+__device__ __forceinline__ void stage_scene(SceneView& sv, const KParams& P, float4* lds, float* sph_stash, bool tab) {
     const SceneTables T = tables_of(P);
     if (geo_staged(GEO)) {
-        // Stage the intersection records once per workgroup, then the Halton tables.
         const StagedF4<uint32_t> n = staged_f4(GEO, T.nT, T.nP, T.nC);
-        RT_LDS_GUARD(16 * (size_t)(n.rec + n.clu) + (GEO == kGeoPairClu ? 4 * (size_t)kHaltonTabFloats : 0));
         stage_records<GEO, NT>(lds, T);
-        if (GEO == kGeoSphLds) {
-            __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
-            sv.xstash = sph_stash;
-        }
+        if (GEO == kGeoSphLds) sv.xstash = sph_stash;
         if (GEO == kGeoPairClu) {
             const uint32_t tab0 = n.rec + n.clu;
-            const bool tab = halton_tables_on(GEO, SMALL, P.spp, L);
             sv.htab = tab ? reinterpret_cast<const float*>(lds + tab0) : nullptr;
-            // the context's tables (filled once, rt_create_ex): a copy, not a fill
             if (tab) copy_halton_tables<NT>(reinterpret_cast<float*>(lds + tab0), P.halton_tab, threadIdx.x);
         }
         __syncthreads();
     }
     bind_scene<GEO, SPH>(sv, T, lds);
+}
+
+template <int B, int GEO, bool SPH, bool SMALL, int L = 1>
+__global__ __launch_bounds__(block_threads(GEO), lockstep_min_waves(GEO, SPH))
+void path_trace_kernel(KParams P) {
+    constexpr uint32_t NT = block_threads(GEO), WR = waves_per_row(GEO), WC = waves_per_col(GEO);
+    extern __shared__ float4 lds[];
+    SceneView sv;
+    __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
+    RT_LDS_GUARD(staged_end(GEO, P, GEO == kGeoPairClu));
+    stage_scene<GEO, SPH, NT>(sv, P, lds, sph_stash, halton_tables_on(GEO, SMALL, P.spp, L));
 
     // wave = 64/L pixels: 8x8 (L=1), 4x4 (L=4), 2x2 (L=16), or one row of 64/L
     // pixels for interleaved rows (launcher's wave_w); workgroup = 2x2 waves
@@ -991,16 +1011,8 @@ thread_local LaunchInfo g_last;
 
 template <int B, int GEO, bool SPH, bool SMALL, int L>
 void note_launch(const char* name, const KParams& P, dim3 grid, uint32_t threads, size_t lds) {
-    LaunchInfo& I = g_last;
-    snprintf(I.kernel, sizeof(I.kernel), "rt::%s<%d, %d, %s, %s, %d>", name, B, GEO,
-             SPH ? "true" : "false", SMALL ? "true" : "false", L);
-    I.lanes = (uint32_t)L;
-    I.tables = halton_tables_on(GEO, SMALL, P.spp, (uint32_t)L) ? 1u : 0u;
-    I.small = SMALL ? 1u : 0u;
-    I.threads = threads;
-    I.grid_x = grid.x;
-    I.grid_y = grid.y;
-    I.lds = (uint32_t)lds;
+    fill_launch_info(g_last, (uint32_t)L, halton_tables_on(GEO, SMALL, P.spp, (uint32_t)L), SMALL, threads, grid, lds,
+                     "rt::%s<%d, %d, %s, %s, %d>", name, B, GEO, SPH ? "true" : "false", SMALL ? "true" : "false", L);
 }
 
 // Dynamic LDS above 64 KB must be allowed per kernel (the compact sphere BVH).
@@ -1064,20 +1076,6 @@ hipError_t launch_h(const KParams& P, size_t lds_bytes, hipStream_t stream) {
                                         : launch_k<B, GEO, SORTED, SPH, false>(P, lds_bytes, stream);
 }
 
-// Picks the sphere and Halton forms of the lockstep (SORTED = false) or the
-// octant-sorted kernel.  The box-cluster layout and the sorted triangle BVH
-// are chosen for triangle-only scenes, kGeoSphLds for sphere scenes only
-// (choose_kernel), whatever P.nS says.  Every layout still instantiates both
-// sphere forms, in this order: the code object's kernels and their order are
-// those of the two pickers this replaces (tools/isa_diff.sh).
-template <int B, int GEO, bool SORTED = false>
-hipError_t launch_g(const KParams& P, size_t lds_bytes, hipStream_t stream) {
-    if constexpr (GEO == (SORTED ? kGeoTriBvh : kGeoPairClu))
-        return launch_h<B, GEO, SORTED, false>(P, lds_bytes, stream);
-    if (GEO == kGeoSphLds || P.nS > 0) return launch_h<B, GEO, SORTED, true>(P, lds_bytes, stream);
-    return launch_h<B, GEO, SORTED, false>(P, lds_bytes, stream);
-}
-
 // The free-running kernel (rt_free.hpp): one pixel per lane, 8x8-pixel waves
 // (one row of 64 pixels for interleaved rows), one-wave workgroups.
 template <int B, int GEO, bool SMALL>
@@ -1102,22 +1100,38 @@ hipError_t launch_free(const KParams& P, size_t lds_bytes, hipStream_t stream) {
     }
 }
 
+// The kernel of layout `geo` (choose_kernel) at B bounces.  A free-running or
+// octant-sorted layout runs the records and walks of its lockstep layout
+// (ray_query_layout), so all three schedulers take their layout and sphere form
+// from dispatch_layout; the Halton form is launch_h's / launch_free's, the lanes
+// launch_t's.  The sorted triangle BVH is chosen for triangle-only scenes
+// (choose_kernel) and has that one form.
+#ifdef RT_DEV_ISA  // ISA-inspection builds only (tools/isa.sh): the render kernels of the headline layouts
+constexpr bool dev_isa_skips(int geo) { return geo != kGeoPairClu && geo != kGeoSphLds && geo != kGeoTriBvh; }
+#else
+constexpr bool dev_isa_skips(int) { return false; }
+#endif
 template <int B>
 hipError_t launch_b(const KParams& P, int geo, size_t lds_bytes, hipStream_t stream) {
-    if (geo == kGeoFreeSph) return launch_free<B, kGeoSphLds>(P, lds_bytes, stream);
-    if (geo == kGeoFreeTri) return launch_free<B, kGeoTriBvh>(P, lds_bytes, stream);
-    if (geo == kGeoPairSorted) return launch_g<B, kGeoPairLds, true>(P, lds_bytes, stream);
-    if (geo == kGeoSortSph) return launch_g<B, kGeoSphLds, true>(P, lds_bytes, stream);
-    if (geo == kGeoSortTri) return launch_g<B, kGeoTriBvh, true>(P, lds_bytes, stream);
-    switch (geo) {
-        case kGeoPairLds: return launch_g<B, kGeoPairLds>(P, lds_bytes, stream);
-        case kGeoPairClu: return launch_g<B, kGeoPairClu>(P, lds_bytes, stream);
-        case kGeoSphLds: return launch_g<B, kGeoSphLds>(P, lds_bytes, stream);
-        case kGeoPairSmem: return launch_g<B, kGeoPairSmem>(P, lds_bytes, stream);
-        case kGeoTriBvh: return launch_g<B, kGeoTriBvh>(P, lds_bytes, stream);
-        case kGeoTriLds: return launch_g<B, kGeoTriLds>(P, lds_bytes, stream);
-        default: return launch_g<B, kGeoTriGlobal>(P, lds_bytes, stream);
-    }
+    const bool free_run = geo == kGeoFreeSph || geo == kGeoFreeTri;
+    const bool sorted = geo == kGeoPairSorted || geo == kGeoSortSph || geo == kGeoSortTri;
+    return dispatch_layout(ray_query_layout(geo), P.nS, [&](auto g, auto sph) {
+        constexpr int GEO = decltype(g)::value;
+        constexpr bool SPH = decltype(sph)::value;
+        if constexpr (dev_isa_skips(GEO)) {
+            return hipErrorInvalidValue;
+        } else {
+            if (free_run) {
+                if constexpr (GEO == kGeoSphLds || GEO == kGeoTriBvh) return launch_free<B, GEO>(P, lds_bytes, stream);
+            } else if (sorted) {
+                if constexpr (GEO == kGeoPairLds || GEO == kGeoSphLds || (GEO == kGeoTriBvh && !SPH))
+                    return launch_h<B, GEO, true, SPH>(P, lds_bytes, stream);
+            } else {
+                return launch_h<B, GEO, false, SPH>(P, lds_bytes, stream);
+            }
+            return hipErrorInvalidValue;  // a layout without that scheduler: choose_kernel gives none
+        }
+    });
 }
 
 }  // namespace
@@ -1177,24 +1191,11 @@ hipError_t launch_path_trace_impl(const KParams& P, uint32_t bounces, SceneMem m
 #else
     const size_t lds_req = lds_total;
 #endif
-#ifdef RT_DEV_ISA  // ISA-inspection builds only (tools/isa.sh): the two headline layouts at B = 3
-    if (bounces != 3) return hipErrorInvalidValue;
-    if (geo == kGeoFreeSph) return launch_free<3, kGeoSphLds>(P, lds_req, stream);
-    if (geo == kGeoFreeTri) return launch_free<3, kGeoTriBvh>(P, lds_req, stream);
-    if (geo == kGeoSortSph) return launch_g<3, kGeoSphLds, true>(P, lds_req, stream);
-    if (geo == kGeoSortTri) return launch_g<3, kGeoTriBvh, true>(P, lds_req, stream);
-    if (geo == kGeoTriBvh) return launch_g<3, kGeoTriBvh>(P, lds_req, stream);
-    return geo == kGeoPairClu ? launch_g<3, kGeoPairClu>(P, lds_req, stream)
-                              : launch_g<3, kGeoSphLds>(P, lds_req, stream);
+#ifdef RT_DEV_ISA  // ISA-inspection builds only (tools/isa.sh): the render kernels at B = 3 alone
+    return bounces == 3 ? launch_b<3>(P, geo, lds_req, stream) : hipErrorInvalidValue;
+#else
+    return dispatch_bounces(bounces, [&](auto b) { return launch_b<decltype(b)::value>(P, geo, lds_req, stream); });
 #endif
-    switch (bounces) {
-        case 0: return launch_b<0>(P, geo, lds_req, stream);
-        case 1: return launch_b<1>(P, geo, lds_req, stream);
-        case 2: return launch_b<2>(P, geo, lds_req, stream);
-        case 3: return launch_b<3>(P, geo, lds_req, stream);
-        case 4: return launch_b<4>(P, geo, lds_req, stream);
-        default: return hipErrorInvalidValue;
-    }
 }
 }  // namespace
 
@@ -1302,13 +1303,11 @@ __global__ __launch_bounds__(kBlockThreads) void wave_masks_kernel(KParams P, ui
                                                                    uint32_t n_waves, uint32_t kWX, uint32_t kWY) {
     const uint32_t w = wave_uniform(blockIdx.x * (kBlockThreads / 64u) + (threadIdx.x >> 6));
     if (w >= n_waves) return;  // wave-uniform
-    const uint32_t nP = P.nP, nC = P.nC;  // 1..32 pairs (wave_mask_grid)
-    const float* pair = reinterpret_cast<const float*>(P.pair_isect);
-    const uint32_t wx0 = (w % waves_x) * kWX, wj0 = (w / waves_x) * kWY;
-    const float y0 = (float)(P.row_start + wj0 * P.row_step);
-    const float y1 = (float)(P.row_start + (wj0 + kWY - 1u) * P.row_step);
-    const Beam beam = make_beam(ld_f3(P.cam_pos), ld_f3(P.cam_u), ld_f3(P.cam_v), ld_f3(P.cam_w), P.halfW, P.halfH,
-                                (float)P.W, (float)P.H, (float)wx0, (float)(wx0 + kWX - 1u), y0, y1);
+    const float* pair = reinterpret_cast<const float*>(P.pair_isect);  // 1..32 pairs (wave_mask_grid)
+    const Beam beam = wave_beam(P, (w % waves_x) * kWX, (w / waves_x) * kWY, kWX, kWY);
+    const uint32_t nP = P.nP, nC = P.nC;
+    // the two masks, spelled out here and in path_counts_kernel: through shared routines
+    // both kernels compile differently (tools/isa_diff.sh)
     const uint32_t k = threadIdx.x & 63u;
     const uint32_t kc = min(k, nP - 1u);  // lanes past the last pair re-test it (discarded)
     const bool keep = !beam_excludes_pair(beam, pair + 4u * kPairF4 * kc);

@@ -2,8 +2,12 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include <type_traits>
 
 #include "rt_math.h"
 #include "rt_raydomain.h"
@@ -266,6 +270,23 @@ struct LaunchInfo {
     char kernel[96];
     uint32_t lanes, tables, small, threads, grid_x, grid_y, lds;
 };
+// THE way a launcher fills one: the kernel's name as rt_last_launch returns it
+// (printf-style, last), then the fields in the order of the record.
+__attribute__((format(printf, 8, 9))) inline void fill_launch_info(LaunchInfo& I, uint32_t lanes, bool tables,
+                                                                   bool small, uint32_t threads, dim3 grid, size_t lds,
+                                                                   const char* name_fmt, ...) {
+    va_list ap;
+    va_start(ap, name_fmt);
+    vsnprintf(I.kernel, sizeof(I.kernel), name_fmt, ap);
+    va_end(ap);
+    I.lanes = lanes;
+    I.tables = tables ? 1u : 0u;
+    I.small = small ? 1u : 0u;
+    I.threads = threads;
+    I.grid_x = grid.x;
+    I.grid_y = grid.y;
+    I.lds = (uint32_t)lds;
+}
 // Where the workgroup reads the intersection records from.
 // rt_walk_scheduler (include/rtpt.h)
 constexpr uint32_t kWalkAuto = 0, kWalkLockstep = 1, kWalkFree = 2, kWalkSorted = 3;
@@ -327,6 +348,40 @@ constexpr int ray_query_layout(int lay) {
            : (lay == kLayFreeTri || lay == kLaySortTri) ? (int)kLayTriBvh
            : lay == kLayPairSorted                      ? (int)kLayPairLds
                                                         : lay;
+}
+// ---- the launchers' dispatch ------------------------------
+// A run-time bounce count as a compile-time one: f(integral_constant<int, B>)
+// for bounces = B in 0..4, hipErrorInvalidValue for every other count.
+template <typename F>
+hipError_t dispatch_bounces(uint32_t bounces, F&& f) {
+    switch (bounces) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// THE rule of layout and sphere form, for every launcher of a lockstep layout
+// (`lay` after ray_query_layout where the context's may be a free or sorted
+// one): f(integral_constant<int, GEO>, bool_constant<SPH>).  choose_kernel gives
+// the box-cluster layout to triangle-only scenes and the sphere layout to sphere
+// scenes only, so these two have one form; every other layout has both, picked
+// by the scene's sphere count nS.  Not a lockstep layout: hipErrorInvalidValue.
+template <typename F>
+hipError_t dispatch_layout(int lay, uint32_t nS, F&& f) {
+    auto by_spheres = [&](auto geo) { return nS > 0 ? f(geo, std::true_type{}) : f(geo, std::false_type{}); };
+    switch (lay) {
+        case kLayTriLds: return by_spheres(std::integral_constant<int, kLayTriLds>{});
+        case kLayPairLds: return by_spheres(std::integral_constant<int, kLayPairLds>{});
+        case kLayTriGlobal: return by_spheres(std::integral_constant<int, kLayTriGlobal>{});
+        case kLayPairSmem: return by_spheres(std::integral_constant<int, kLayPairSmem>{});
+        case kLayTriBvh: return by_spheres(std::integral_constant<int, kLayTriBvh>{});
+        case kLayPairClu: return f(std::integral_constant<int, kLayPairClu>{}, std::false_type{});
+        case kLaySphLds: return f(std::integral_constant<int, kLaySphLds>{}, std::true_type{});
+        default: return hipErrorInvalidValue;
+    }
 }
 // THE dynamic LDS of a query workgroup of layout `lay` (after ray_query_layout):
 // staged_f4 and nothing else (no Halton tables).  The kernel places its arrays

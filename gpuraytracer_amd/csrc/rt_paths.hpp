@@ -37,10 +37,6 @@
 
 namespace {
 
-__device__ __forceinline__ float path_lane_copy(float v, int src) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
 // The render's bounce chain from the closest hit (id, t) of s.o, s.d.
 template <int B, int GEO, bool SPH, bool SMALL>
 __device__ __forceinline__ void trace_from_hit(const KParams& P, const SceneView& sv, PathState& s, int id,
@@ -60,10 +56,7 @@ constexpr int kPathMiss = -1, kPathUntraced = -2;  // a first segment without a 
 }  // namespace
 
 template <int B, int GEO, bool SPH, bool SMALL, int L>
-__global__ __launch_bounds__(block_threads(GEO),
-                             SPH ? kMinWavesPerEuSph
-                                 : (GEO == kGeoPairClu ? kMinWavesPerEuClu
-                                                       : (GEO == kGeoTriBvh ? RT_TRI_WAVES : kMinWavesPerEu)))
+__global__ __launch_bounds__(block_threads(GEO), lockstep_min_waves(GEO, SPH))
 void path_query_kernel(KParams P, const float4* __restrict__ rays, const uint32_t* __restrict__ seeds,
                        float4* __restrict__ radiance, uint2* __restrict__ hits, uint32_t n, uint32_t chunk,
                        uint64_t seed_key, RayDomain dom) {
@@ -71,24 +64,10 @@ void path_query_kernel(KParams P, const float4* __restrict__ rays, const uint32_
     constexpr uint32_t NT = block_threads(GEO), RPP = NT / L;  // rays per pass
     extern __shared__ float4 lds[];
     SceneView sv;
-    const SceneTables T = tables_of(P);
-    if (geo_staged(GEO)) {
-        const StagedF4<uint32_t> nf = staged_f4(GEO, T.nT, T.nP, T.nC);
-        const bool tab = path_query_tables_on(GEO, SMALL, P.spp, L);  // halton_tables_on, inlined
-        RT_LDS_GUARD(16 * (size_t)(nf.rec + nf.clu) + (tab ? 4 * (size_t)kHaltonTabFloats : 0));
-        stage_records<GEO, NT>(lds, T);
-        if (GEO == kGeoSphLds) {
-            __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
-            sv.xstash = sph_stash;
-        }
-        if (GEO == kGeoPairClu) {
-            const uint32_t tab0 = nf.rec + nf.clu;
-            sv.htab = tab ? reinterpret_cast<const float*>(lds + tab0) : nullptr;
-            if (tab) copy_halton_tables<NT>(reinterpret_cast<float*>(lds + tab0), P.halton_tab, threadIdx.x);
-        }
-        __syncthreads();
-    }
-    bind_scene<GEO, SPH>(sv, T, lds);
+    __shared__ float sph_stash[GEO == kGeoSphLds ? 6 * kSphBlockThreads : 1];
+    const bool tab = path_query_tables_on(GEO, SMALL, P.spp, L);  // halton_tables_on, inlined
+    RT_LDS_GUARD(staged_end(GEO, P, tab));
+    stage_scene<GEO, SPH, NT>(sv, P, lds, sph_stash, tab);
 
     // per ray, in LDS so that they are not live across the walks: seed +
     // sample_base, the first hit, and at L = 16 the running sum
@@ -115,13 +94,12 @@ void path_query_kernel(KParams P, const float4* __restrict__ rays, const uint32_
             int id = in ? kPathMiss : kPathUntraced;
             const unsigned long long inmask = __builtin_amdgcn_ballot_w64(in);
             if (inmask != 0ull) {  // wave-uniform
+                // the substitution of ray_query_kernel (rt_rays.hip), spelled out (tools/isa_diff.sh)
                 const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)inmask) - 1);
-                f3 qo{in ? o.x : path_lane_copy(o.x, src), in ? o.y : path_lane_copy(o.y, src),
-                      in ? o.z : path_lane_copy(o.z, src)};
-                f3 qd{in ? d.x : path_lane_copy(d.x, src), in ? d.y : path_lane_copy(d.y, src),
-                      in ? d.z : path_lane_copy(d.z, src)};
-                const float qtmin = in ? tmin : path_lane_copy(tmin, src);
-                float qbest = in ? tmax : path_lane_copy(tmax, src);
+                f3 qo{in ? o.x : lane_copy(o.x, src), in ? o.y : lane_copy(o.y, src), in ? o.z : lane_copy(o.z, src)};
+                f3 qd{in ? d.x : lane_copy(d.x, src), in ? d.y : lane_copy(d.y, src), in ? d.z : lane_copy(d.z, src)};
+                const float qtmin = in ? tmin : lane_copy(tmin, src);
+                float qbest = in ? tmax : lane_copy(tmax, src);
                 const int qid = closest_hit<GEO, SPH, /*CULL*/ false, 1>(sv, qo, qd, qtmin, &qbest);
                 if (in && qid >= 0) {
                     best = qbest;
@@ -235,31 +213,6 @@ hipError_t launch_paths_h(const KParams& P, const PathQueryArgs& A, hipStream_t 
     return launch_paths_tl<B, GEO, SPH, false, 1>(P, A, stream);
 }
 
-template <int B, int GEO>
-hipError_t launch_paths_g(const KParams& P, const PathQueryArgs& A, hipStream_t stream) {
-    if constexpr (GEO == kGeoPairClu) {
-        return launch_paths_h<B, GEO, false>(P, A, stream);
-    } else if constexpr (GEO == kGeoSphLds) {
-        return launch_paths_h<B, GEO, true>(P, A, stream);
-    } else {
-        return P.nS > 0 ? launch_paths_h<B, GEO, true>(P, A, stream) : launch_paths_h<B, GEO, false>(P, A, stream);
-    }
-}
-
-template <int B>
-hipError_t launch_paths_b(const KParams& P, const PathQueryArgs& A, int geo, hipStream_t stream) {
-    switch (geo) {
-        case kGeoPairLds: return launch_paths_g<B, kGeoPairLds>(P, A, stream);
-        case kGeoPairClu: return launch_paths_g<B, kGeoPairClu>(P, A, stream);
-        case kGeoSphLds: return launch_paths_g<B, kGeoSphLds>(P, A, stream);
-        case kGeoPairSmem: return launch_paths_g<B, kGeoPairSmem>(P, A, stream);
-        case kGeoTriBvh: return launch_paths_g<B, kGeoTriBvh>(P, A, stream);
-        case kGeoTriLds: return launch_paths_g<B, kGeoTriLds>(P, A, stream);
-        case kGeoTriGlobal: return launch_paths_g<B, kGeoTriGlobal>(P, A, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_path_query(const KParams& P, const PathQueryArgs& A, uint32_t bounces, SceneMem mem,
@@ -268,15 +221,11 @@ hipError_t launch_path_query(const KParams& P, const PathQueryArgs& A, uint32_t 
     const SceneTables T = tables_of(P);
     // the lockstep form of the context's layout, as a ray query takes it
     const int geo = ray_query_layout(choose_kernel(T, P.sph_lds != nullptr, bounces, mem, kWalkLockstep).layout);
-    hipError_t e;
-    switch (bounces) {
-        case 0: e = launch_paths_b<0>(P, A, geo, stream); break;
-        case 1: e = launch_paths_b<1>(P, A, geo, stream); break;
-        case 2: e = launch_paths_b<2>(P, A, geo, stream); break;
-        case 3: e = launch_paths_b<3>(P, A, geo, stream); break;
-        case 4: e = launch_paths_b<4>(P, A, geo, stream); break;
-        default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = dispatch_bounces(bounces, [&](auto b) {
+        return dispatch_layout(geo, P.nS, [&](auto g, auto sph) {
+            return launch_paths_h<decltype(b)::value, decltype(g)::value, decltype(sph)::value>(P, A, stream);
+        });
+    });
     if (info) *info = g_last;
     return e;
 }

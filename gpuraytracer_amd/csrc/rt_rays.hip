@@ -65,10 +65,6 @@ __device__ __forceinline__ void exact_scan(const SceneTables& T, f3 o, f3 d, flo
     }
 }
 
-__device__ __forceinline__ float lane_copy(float v, int src) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
 template <int GEO, bool SPH, bool ANY>
 __global__ __launch_bounds__(kBlockThreads) void ray_query_kernel(RayQueryParams P) {
     extern __shared__ float4 lds[];
@@ -99,6 +95,8 @@ __global__ __launch_bounds__(kBlockThreads) void ray_query_kernel(RayQueryParams
         int id = -1;
         const unsigned long long inmask = __builtin_amdgcn_ballot_w64(in);
         if (inmask != 0ull) {  // wave-uniform
+            // the substitution, spelled out here and in path_query_kernel: through a shared routine
+            // every instantiation of both kernels compiles differently (tools/isa_diff.sh)
             const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)inmask) - 1);
             f3 qo{in ? o.x : lane_copy(o.x, src), in ? o.y : lane_copy(o.y, src), in ? o.z : lane_copy(o.z, src)};
             f3 qd{in ? d.x : lane_copy(d.x, src), in ? d.y : lane_copy(d.y, src), in ? d.z : lane_copy(d.z, src)};
@@ -143,16 +141,8 @@ thread_local LaunchInfo g_last_rays;
 template <int GEO, bool SPH, bool ANY>
 hipError_t launch_q(const RayQueryParams& P, size_t lds_bytes, hipStream_t stream) {
     const dim3 grid((uint32_t)(((uint64_t)P.n + kRayChunk - 1) / kRayChunk));
-    LaunchInfo& I = g_last_rays;
-    snprintf(I.kernel, sizeof(I.kernel), "rt::ray_query_kernel<%d, %s, %s>", GEO, SPH ? "true" : "false",
-             ANY ? "true" : "false");
-    I.lanes = 0;
-    I.tables = 0;
-    I.small = 0;
-    I.threads = kBlockThreads;
-    I.grid_x = grid.x;
-    I.grid_y = 1;
-    I.lds = (uint32_t)lds_bytes;
+    fill_launch_info(g_last_rays, 0, false, false, kBlockThreads, grid, lds_bytes, "rt::ray_query_kernel<%d, %s, %s>",
+                     GEO, SPH ? "true" : "false", ANY ? "true" : "false");
     hipLaunchKernelGGL((ray_query_kernel<GEO, SPH, ANY>), grid, dim3(kBlockThreads), lds_bytes, stream,
                        P);  // ray_query_lds_bytes of the layout
     return hipGetLastError();
@@ -164,15 +154,6 @@ hipError_t launch_a(const RayQueryParams& P, size_t lds_bytes, hipStream_t strea
                                 : launch_q<GEO, SPH, false>(P, lds_bytes, stream);
 }
 
-// The box-cluster layout serves triangle-only scenes, the sphere layout sphere
-// scenes only (choose_kernel); every other layout has both sphere forms.
-template <int GEO>
-hipError_t launch_s(const RayQueryParams& P, size_t lds_bytes, hipStream_t stream) {
-    if constexpr (GEO == kGeoPairClu) return launch_a<GEO, false>(P, lds_bytes, stream);
-    else if constexpr (GEO == kGeoSphLds) return launch_a<GEO, true>(P, lds_bytes, stream);
-    else return P.tab.nS > 0 ? launch_a<GEO, true>(P, lds_bytes, stream) : launch_a<GEO, false>(P, lds_bytes, stream);
-}
-
 }  // namespace
 
 hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t stream, LaunchInfo* info) {
@@ -180,17 +161,9 @@ hipError_t launch_ray_query(const RayQueryParams& P, SceneMem mem, hipStream_t s
     const KernelChoice kc = choose_kernel(P.tab, P.sph_compact != 0u, 3, mem, kWalkLockstep);
     const int geo = ray_query_layout(kc.layout);
     const size_t lds = ray_query_lds_bytes(geo, P.tab.nT, P.tab.nP, P.tab.nC);
-    hipError_t e;
-    switch (geo) {
-        case kGeoTriLds: e = launch_s<kGeoTriLds>(P, lds, stream); break;
-        case kGeoPairLds: e = launch_s<kGeoPairLds>(P, lds, stream); break;
-        case kGeoTriGlobal: e = launch_s<kGeoTriGlobal>(P, lds, stream); break;
-        case kGeoPairSmem: e = launch_s<kGeoPairSmem>(P, lds, stream); break;
-        case kGeoTriBvh: e = launch_s<kGeoTriBvh>(P, lds, stream); break;
-        case kGeoPairClu: e = launch_s<kGeoPairClu>(P, lds, stream); break;
-        case kGeoSphLds: e = launch_s<kGeoSphLds>(P, lds, stream); break;
-        default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = dispatch_layout(geo, P.tab.nS, [&](auto g, auto sph) {
+        return launch_a<decltype(g)::value, decltype(sph)::value>(P, lds, stream);
+    });
     if (info) *info = g_last_rays;
     return e;
 }

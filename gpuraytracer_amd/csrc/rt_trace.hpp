@@ -262,6 +262,11 @@ __device__ __forceinline__ uint32_t octant(f3 d) {
 __device__ __forceinline__ uint32_t wave_uniform(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
+// v of lane src (wave-uniform): the query kernels of the caller's own rays run a
+// copy of the wave's first in-domain ray on the lanes without one (rt_rays.hip)
+__device__ __forceinline__ float lane_copy(float v, int src) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
 
 // Sphere-BVH walks over the 32-B nodes (the sphere scenes of the pair, single
 // and global layouts; the sphere kernel walks the leaf-box BVH below).
