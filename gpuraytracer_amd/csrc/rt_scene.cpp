@@ -261,6 +261,36 @@ static float culling_margin(const rt_float3* verts, uint32_t n_tri, const Sphere
     return rel * ext;  // rel = 1: the extent itself
 }
 
+// The padding of the sphere BVH's boxes.  The sphere test
+// (rt_trace.hpp sph_test) takes disc = b*b - 4a*cc > 0 for a hit, a difference
+// of two terms of size 4a*D^2, D = |o - c|.  Rounding moves it by up to
+// 80 eps a D^2 (eps = 2^-24: 9 eps of b*b from oc, the fma-dot and the square;
+// 10 eps of 4a*cc from oc, dot(oc, oc), the subtraction of r^2, a and the
+// product; 1 eps of the difference), and exactly disc = 4a (r^2 - p^2) with p
+// the distance of the centre from the ray's line.  So the test, and with it the
+// id-ordered scan the walks must equal, accepts rays that pass the centre
+// within sqrt(r^2 + 20 eps D^2), at a t whose point lies within that distance
+// of the centre too: a box has to hold that larger sphere.  The culling margin
+// is linear in the extent, this term quadratic: with the camera at (0, 0, 900)
+// and spheres of radius 0.1 the scan accepted rays 0.24 beside a sphere, the
+// boxes padded by 4e-5 * 900 did not, and the sphere kernels lost those hits.
+// D is bounded by the exactness domain of a ray's origin, sqrt(3) * extent,
+// plus the farthest centre; the smallest radius gives the largest padding.
+static float sphere_margin(const SphereGPU* sph, uint32_t n_sph, float extent, float margin) {
+    double c_max = 0.0, r_min = INFINITY;
+    for (uint32_t k = 0; k < n_sph; ++k) {
+        const double x = sph[k].center.x, y = sph[k].center.y, z = sph[k].center.z;
+        const double c = sqrt(x * x + y * y + z * z), r = fabs((double)sph[k].radius);
+        if (isfinite(c)) c_max = fmax(c_max, c);
+        if (isfinite(r)) r_min = fmin(r_min, r);
+    }
+    if (!n_sph || !isfinite(r_min)) return margin;
+    const double D = sqrt(3.0) * (double)extent + c_max;
+    const double pad = sqrt(r_min * r_min + 20.0 * ldexp(1.0, -24) * D * D) - r_min;
+    // a non-finite extent made the margin itself infinite already
+    return isfinite(pad) ? nextafterf((float)((double)margin + pad), INFINITY) : margin;
+}
+
 // BVH over the spheres (median split of the centroids on the longest axis,
 // one sphere per leaf by default), emitted as 8 depth-first layouts, one per ray-direction
 // octant: at every inner node the child on the near side of the split for that
@@ -1234,6 +1264,27 @@ bool compile_scene(const CameraGPU& cam, const MaterialGPU* mats, const rt_float
     const f3 w = -normalize(from_abi(cam.direction));                    // :137
     const f3 u = normalize(cross(from_abi(cam.up), w));                  // :138
     const f3 v = normalize(cross(w, u));                                 // :139
+    // The same rule as for the portrait frame: a camera whose derived constants
+    // are not all finite makes every camera ray NaN.  Reject instead of rendering NaNs.
+    if (!isfinite(c.halfW) || !isfinite(c.halfH)) {
+        *err = "camera horizontalFov: tan(horizontalFov / 2) is not finite";
+        return false;
+    }
+    const auto unit = [](const f3& a) { return dot(a, a) > 0.5f && isfinite(dot(a, a)); };  // false for NaN
+    if (!unit(w)) {
+        *err = "camera direction: normalize(direction) is not a unit vector (zero length, or its square overflows)";
+        return false;
+    }
+    // cross(up, w) of an up along an oblique direction is rounding noise of w, which
+    // normalizes to some finite roll: the inputs' own cross product tells (in double
+    // a product of two floats is exact and cannot underflow)
+    const double ux = cam.up.x, uy = cam.up.y, uz = cam.up.z;
+    const double dx = cam.direction.x, dy = cam.direction.y, dz = cam.direction.z;
+    const bool parallel = uy * dz == uz * dy && uz * dx == ux * dz && ux * dy == uy * dx;
+    if (!unit(u) || !unit(v) || parallel) {
+        *err = "camera up: cross(up, -direction) does not normalize (up is zero, or parallel to direction)";
+        return false;
+    }
     const f3 p = from_abi(cam.position);
     c.pos[0] = p.x; c.pos[1] = p.y; c.pos[2] = p.z;
     c.u[0] = u.x; c.u[1] = u.y; c.u[2] = u.z;
@@ -1290,7 +1341,7 @@ bool compile_scene(const CameraGPU& cam, const MaterialGPU* mats, const rt_float
         }
     }
     out->sph_shade.resize(n_sph);
-    build_sphere_bvh(out, spheres, n_sph, margin, opt);
+    build_sphere_bvh(out, spheres, n_sph, sphere_margin(spheres, n_sph, out->extent, margin), opt);
     for (uint32_t k = 0; k < n_sph; ++k) {
         const SphereGPU& sp = spheres[k];
         const f3 em = from_abi(sp.material.emissive);

@@ -275,6 +275,51 @@ def test_portrait_resolution_is_rejected():
     assert g.Scene.cornell_box(41, 40).describe()["n_triangles"] == 36
 
 
+def _with_camera(**fields):
+    """The 40 x 30 Cornell scene seen through tests/pose_scenes.posed(**fields)."""
+    import pose_scenes
+    return pose_scenes.posed(g.Scene.cornell_box(40, 30), **fields)
+
+
+DEGENERATE_CAMERAS = [
+    ("zero direction", dict(direction=(0.0, 0.0, 0.0)), "direction"),
+    ("signed-zero direction", dict(direction=(-0.0, 0.0, -0.0)), "direction"),
+    ("direction whose square underflows", dict(direction=(0.0, 1e-30, 0.0)), "direction"),
+    ("direction whose square overflows", dict(direction=(0.0, 0.0, -3e19)), "direction"),
+    ("zero up", dict(up=(0.0, 0.0, 0.0)), "up"),
+    ("up parallel to direction", dict(up=(0.0, 0.0, -1.0)), "up"),
+    ("up antiparallel to direction", dict(up=(0.0, 0.0, 2.5)), "up"),
+    ("up parallel to an oblique direction", dict(direction=(1.0, -2.0, 0.5), up=(3.0, -6.0, 1.5)), "up"),
+    ("up so close to direction that the cross product's square underflows", dict(up=(0.0, 1e-25, -1.0)), "up"),
+    ("NaN fov", dict(fov=float("nan")), "horizontalFov"),
+    ("infinite fov", dict(fov=float("inf")), "horizontalFov"),
+    ("negative infinite fov", dict(fov=float("-inf")), "horizontalFov"),
+]
+
+
+@pytest.mark.parametrize("what,fields,word", DEGENERATE_CAMERAS, ids=[c[0] for c in DEGENERATE_CAMERAS])
+def test_degenerate_camera_is_rejected(what, fields, word):
+    """A camera whose derived constants (w = -normalize(direction), u =
+    normalize(cross(up, w)), v, tan(fov / 2); sampling.metal:132-139) are not
+    all finite makes every camera ray NaN.  The boundary refuses it with
+    RT_ERR_INVALID_ARG and names the field, as it refuses a
+    portrait frame."""
+    with pytest.raises(g.RtError) as e:
+        _with_camera(**fields).describe()
+    assert e.value.status == 1 and "camera " + word in str(e.value), (what, str(e.value))
+
+
+def test_unusual_cameras_are_accepted():
+    """What the rule must not refuse: directions and ups of any finite length,
+    an up close to the direction, fovs whose tangent is finite (0, negative,
+    past pi, the float next to pi: tanf(pi / 2) is finite in float32)."""
+    for fields in (dict(direction=(0.0, 0.0, -1e-15)), dict(direction=(3e18, 0.0, -3e18)), dict(up=(0.0, 1e-15, 0.0)),
+                   dict(up=(0.0, 1e-3, -1.0)), dict(up=(3.0, 4.0, 0.0)), dict(up=(1e-18, 0.0, 0.0), direction=(0.0, 0.0, -1e-18)),
+                   dict(direction=(1.0, -2.0, 0.5), up=(3.0, -6.0, 1.501)), dict(fov=0.0),
+                   dict(fov=-0.5), dict(fov=4.0), dict(fov=float(np.float32(np.pi)))):
+        assert _with_camera(**fields).describe()["n_triangles"] == 36, fields
+
+
 def test_library_carries_the_tree_source_hash():
     """librtpt.so was built from exactly these sources (rt_build_sha, compiled
     in by the Makefile from gpuraytracer_amd/srchash.py); the loader refuses a

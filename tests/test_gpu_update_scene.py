@@ -16,7 +16,8 @@ keeps its topology and gets its boxes from the device refit (rt_refit.hip).
                  equal a fresh context's
   5  rebuild     RT_UPDATE_REBUILD gives a fresh context's tree
   6  state       the running sum is dropped, argument errors name the field
-                 and leave the old scene in place, update_info counts successes
+                 and leave the old scene in place (a degenerate camera among
+                 them: refused, never rendered), update_info counts successes
 
 The scenes are those of tests/update_scenes.py at the 40 x 24 frames of
 tests/tri_bvh_scenes.py."""
@@ -27,6 +28,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import pose_scenes
 import ray_sets as rs
 import tri_bvh_scenes as ts
 import tri_bvh_tree as tt
@@ -329,6 +331,17 @@ def test_argument_errors_leave_the_old_scene():
     nan_cam = CameraGPU.from_buffer_copy(bytes(base.camera))
     nan_cam.position.x = float("nan")
     rejected = Scene(nan_cam, base.materials, base.vertices, base.light)
+
+    def degenerate(**fields):  # cameras whose rays would all be NaN: refused, never rendered
+        return pose_scenes.posed(base, **fields)
+
+    d = tuple(base.camera.direction)
+    degenerates = [(degenerate(direction=(0.0, 0.0, 0.0)).desc(), 0, "camera direction"),
+                   (degenerate(up=(0.0, 0.0, 0.0)).desc(), 0, "camera up"),
+                   (degenerate(up=d).desc(), 0, "camera up"),
+                   (degenerate(up=tuple(-2.0 * c for c in d)).desc(), 0, "camera up"),
+                   (degenerate(fov=float("inf")).desc(), 0, "camera horizontalFov"),
+                   (degenerate(fov=float("nan")).desc(), _native.RT_UPDATE_REBUILD, "camera horizontalFov")]
     with Renderer(base, seeds=seeds, options=ts.options(name)) as r:
         with pytest.raises(RtError) as e:
             r.update_info()
@@ -336,7 +349,7 @@ def test_argument_errors_leave_the_old_scene():
         cases = [(other_count.desc(), 0, "n_triangles"), (with_sphere.desc(), 0, "n_spheres"),
                  (other_size.desc(), 0, "resolution"), (base.desc(device=1), 0, "device"),
                  (us.build(name, "shift").desc(), 0x2, "flags"), (us.build(name, "shift").desc(), 0x80000001, "flags"),
-                 (rejected.desc(), 0, "camera")]
+                 (rejected.desc(), 0, "camera")] + degenerates
         for desc, flags, field in cases:
             assert lib.rt_update_scene(r._ctx, ctypes.byref(desc), flags) == INVALID_ARG, field
             assert field in lib.rt_last_error(r._ctx).decode(), (field, lib.rt_last_error(r._ctx))
