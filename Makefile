@@ -16,8 +16,8 @@ HOSTFLAGS := $(COMMON) -D__HIP_PLATFORM_AMD__ -isystem /opt/rocm/include $(EXTRA
 
 # The library's objects, named once: the device ones (.hip) and the host ones
 # (.cpp), which the sanitizer build below compiles a second time.
-DEV_OBJS := rt_kernel.o rt_rays.o rt_aov.o rt_denoise.o rt_adaptive.o rt_mis.o rt_lbvh.o rt_gsah.o rt_refit.o rt_mathcheck.o
-HOST_OBJS := rt_api.o rt_api_host.o rt_scene.o rt_image.o
+DEV_OBJS := rt_kernel.o rt_rays.o rt_aov.o rt_denoise.o rt_reproject.o rt_adaptive.o rt_mis.o rt_lbvh.o rt_gsah.o rt_refit.o rt_mathcheck.o
+HOST_OBJS := rt_api.o rt_api_host.o rt_scene.o rt_camera.o rt_reproject_host.o rt_image.o
 OBJS := $(addprefix $(BLD)/,$(DEV_OBJS) $(HOST_OBJS))
 HDRS := include/rtpt.h include/rt_types.h $(SRC)/rt_math.h $(SRC)/rt_kernel.hpp $(SRC)/rt_scene.hpp $(SRC)/rt_halton.hpp $(SRC)/rt_beam.hpp $(SRC)/rt_shaft.hpp $(SRC)/rt_cluorder.hpp $(SRC)/rt_raydomain.h $(SRC)/rt_pixel.hpp $(SRC)/rt_plan.hpp $(SRC)/rt_wavemask.hpp
 
@@ -39,7 +39,8 @@ $(BLD)/%.o: $(SRC)/%.hip $(HDRS) $(SRC)/rt_trace.hpp | $(BLD)
 
 # the device-vs-host check of the shared scalar functions
 $(BLD)/rt_mathcheck.o $(BLD)/rt_image.o $(BLD)/rt_api_host.o: $(SRC)/rt_half.h $(SRC)/rt_mathcheck.hpp
-$(BLD)/rt_api_host.o: $(SRC)/rt_api_internal.hpp
+$(BLD)/rt_api_host.o $(BLD)/rt_reproject_host.o: $(SRC)/rt_api_internal.hpp $(SRC)/rt_reproject.hpp
+$(BLD)/rt_reproject.o: $(SRC)/rt_reproject.hpp
 $(BLD)/rt_kernel.o: $(SRC)/rt_free.hpp $(SRC)/rt_counts.hpp $(SRC)/rt_paths.hpp
 
 $(BLD)/rt_api.o: $(SRC)/rt_api.cpp $(ALLSRC) | $(BLD)
@@ -81,6 +82,8 @@ $(ASAN)/%.o: $(SRC)/%.cpp $(HDRS) | $(ASAN)
 
 $(ASAN)/rt_image.o $(ASAN)/rt_api_host.o: $(SRC)/rt_half.h
 $(ASAN)/rt_api_host.o: $(SRC)/rt_api_internal.hpp $(SRC)/rt_mathcheck.hpp
+$(ASAN)/rt_api_host.o $(ASAN)/rt_reproject_host.o: $(SRC)/rt_reproject.hpp
+$(ASAN)/rt_reproject_host.o: $(SRC)/rt_api_internal.hpp
 
 $(ASAN)/librtpt.so: $(ASAN_HOST) $(addprefix $(BLD)/,$(DEV_OBJS))
 	$(HOSTCXX) -shared $(SAN) -o $@ $^ -L/opt/rocm/lib -lamdhip64 -lrccl -Wl,-rpath,/opt/rocm/lib
@@ -94,8 +97,17 @@ asan: $(ASAN)/librtpt.so $(ASAN)/liboracle.so
 asan-test: asan
 	RTPT_SAN_DIR=$(abspath $(ASAN)) RTPT_SAN_RT=$(ASAN_RT) python3 tests/run_sanitized.py
 
+# Stand-alone sanitizer run of rt_reproject_host (tools/reproject_host_check.cpp):
+# a program with its own main, linked with the sanitized host objects it needs
+# and nothing of the device side, over adversarial buffers and tiny frames.
+$(ASAN)/reproject_host_check: tools/reproject_host_check.cpp $(ASAN)/rt_reproject_host.o $(ASAN)/rt_camera.o
+	$(HOSTCXX) $(HOSTFLAGS) $(SAN:-shared-libasan=) -o $@ $^
+
+reproject-check: $(ASAN)/reproject_host_check
+	$(ASAN)/reproject_host_check
+
 clean:
 	rm -rf $(BLD) $(ASAN) $(PKG)/librtpt.so $(PKG)/rtrace
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle clean asan asan-test
+.PHONY: all lib oracle clean asan asan-test reproject-check

@@ -15,7 +15,9 @@ reference's Swift host API, used by the tests and ``bench.py``:
   ``denoise`` / ``render_denoised`` filter a low-spp render with them;
   ``render_counts`` renders one sample count per pixel, ``plan_samples`` makes
   such counts from a pilot render and ``render_adaptive`` runs the pipeline;
-  ``trace_paths`` path-traces radiance along the caller's own rays.
+  ``trace_paths`` path-traces radiance along the caller's own rays;
+  ``reproject`` / ``render_temporal`` carry accumulated colour from frame to
+  frame under a moving camera.
 
 There is no CPU fallback: importing fails loudly when ``librtpt.so`` has not
 been built (``make`` or ``__graft_entry__.build()``), and rendering fails
@@ -24,9 +26,9 @@ loudly without a HIP device.
 from __future__ import annotations
 
 from ._native import (ABI_VERSION, RT_AOV_CENTER, RT_RAYS_CHUNK, AovBuffers, AovParams, CameraGPU, DenoiseBuffers,
-                      DenoiseParams, MaterialGPU, PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, RtError, SphereGPU, SquareLightGPU, float3, lib, library_path)
+                      DenoiseParams, MaterialGPU, PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, ReprojectBuffers, ReprojectParams, RtError, SphereGPU, SquareLightGPU, float3, lib, library_path)
 from .host import (DEFAULT_SEED_KEY, MisParams, Options, RenderParams, Renderer, Scene, comm_unique_id,
-                   math_sums, math_values, place_tiles_host, plan_samples_host, seed_splitmix, tile_layout, tonemap_rgba8)
+                   math_sums, math_values, place_tiles_host, plan_samples_host, reproject_host, seed_splitmix, tile_layout, tonemap_rgba8)
 
 __all__ = [
     "ABI_VERSION", "CameraGPU", "MaterialGPU", "SphereGPU", "SquareLightGPU", "float3",
@@ -34,5 +36,5 @@ __all__ = [
     "DEFAULT_SEED_KEY", "seed_splitmix", "tonemap_rgba8", "comm_unique_id", "tile_layout",
     "place_tiles_host", "RT_RAYS_CHUNK", "RT_AOV_CENTER", "AovParams", "AovBuffers",
     "DenoiseParams", "DenoiseBuffers", "math_values", "math_sums", "PlanParams", "PlanStats",
-    "RT_PLAN_RELATIVE", "plan_samples_host", "PathParamsC",
+    "RT_PLAN_RELATIVE", "plan_samples_host", "PathParamsC", "ReprojectParams", "ReprojectBuffers", "reproject_host",
 ]

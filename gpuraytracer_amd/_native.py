@@ -210,6 +210,21 @@ class DenoiseBuffers(ctypes.Structure):  # rt_denoise_buffers
 assert ctypes.sizeof(DenoiseParams) == 32 and ctypes.sizeof(DenoiseBuffers) == 40 and DenoiseBuffers.out.offset == 32
 
 
+class ReprojectParams(ctypes.Structure):  # rt_reproject_params
+    _fields_ = [("max_history", ctypes.c_uint32), ("normal_cos_min", ctypes.c_float), ("plane_rel", ctypes.c_float),
+                ("weight_min", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class ReprojectBuffers(ctypes.Structure):  # rt_reproject_buffers
+    _fields_ = [("color", ctypes.c_void_p * 2), ("history", ctypes.c_void_p * 2), ("hit", ctypes.c_void_p),
+                ("normal_depth", ctypes.c_void_p), ("prev_hit", ctypes.c_void_p),
+                ("prev_normal_depth", ctypes.c_void_p), ("out", ctypes.c_void_p * 2)]
+
+
+assert ctypes.sizeof(ReprojectParams) == 32 and ctypes.sizeof(ReprojectBuffers) == 80
+assert ReprojectBuffers.hit.offset == 32 and ReprojectBuffers.out.offset == 64
+
+
 RT_PLAN_RELATIVE = 0x800  # rt_plan_samples: weight by the relative luminance change
 
 
@@ -273,6 +288,13 @@ SIGNATURES = {
     "rt_denoise_params_default": (None, [ctypes.POINTER(DenoiseParams)]),
     "rt_denoise": (ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers)]),
     "rt_denoise_async": (ctypes.c_int, [_P, ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseBuffers), _P]),
+    "rt_reproject_params_default": (None, [ctypes.POINTER(ReprojectParams)]),
+    "rt_reproject": (ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams), ctypes.POINTER(CameraGPU),
+                                    ctypes.POINTER(ReprojectBuffers)]),
+    "rt_reproject_async": (ctypes.c_int, [_P, ctypes.POINTER(ReprojectParams), ctypes.POINTER(CameraGPU),
+                                          ctypes.POINTER(ReprojectBuffers), _P]),
+    "rt_reproject_host": (ctypes.c_int, [ctypes.POINTER(CameraGPU), ctypes.POINTER(CameraGPU),
+                                         ctypes.POINTER(ReprojectParams), ctypes.POINTER(ReprojectBuffers)]),
     "rt_render_counts": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P, _P]),
     "rt_render_counts_async": (ctypes.c_int, [_P, ctypes.POINTER(RenderParamsC), _P, _P, _P, _P]),
     "rt_plan_params_default": (None, [ctypes.POINTER(PlanParams)]),

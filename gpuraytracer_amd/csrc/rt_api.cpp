@@ -158,6 +158,7 @@ struct rt_ctx {
     DevBuf d_ray_seeds, d_radiance;  // staging for host ray seeds and radiance (rt_trace_paths)
     DevBuf d_aov[3];               // staging for host feature buffers (rt_render_aov)
     DevBuf d_den[6];               // rt_denoise: the (D, V) ping-pong, then staging for the four host inputs
+    DevBuf d_rep[8];               // rt_reproject: staging for the eight host inputs (the outputs: the staged colours)
     DevBuf d_counts, d_totals;     // staging for host counts and totals (rt_render_counts, rt_plan_samples)
     DevBuf d_plan_in[2];           // staging for the planner's two host images
     DevBuf d_plan;                 // the planner's accumulators (rt::PlanStats)
@@ -1108,6 +1109,56 @@ int denoise_impl(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buffers
     return finish(c, stream, sync, "denoise execution");
 }
 
+// rt_reproject / rt_reproject_async: one launch of reproject_kernel
+// (rt_reproject.hip) on whole frames, the context's camera against
+// `prev_camera`.  Host buffers go through the context's staging buffers on its
+// own stream; the staged outputs are the staged colours (out[k] may be color[k]).
+int reproject_impl(rt_ctx* c, const rt_reproject_params* p, const CameraGPU* prev_camera,
+                   const rt_reproject_buffers* b, bool dev, hipStream_t stream, bool sync) {
+    uint32_t planes = 0;
+    const std::string bad = reproject_check(p, b, RT_OUT_DEVICE, &planes);
+    if (!bad.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_reproject: " + bad);
+    if (!c->broken.empty()) return fail(c, RT_ERR_STATE, c->broken);
+    rt::ReprojectArgs A;
+    std::string why;
+    if (!reproject_args(p, b, c->scene.cam, prev_camera, &A, &why))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_reproject: " + why);
+    const size_t px = (size_t)A.W * (size_t)A.H, bytes = px * sizeof(float4), hit_bytes = px * sizeof(uint2);
+    int st;
+    if (!dev) {
+        // color[0], color[1], history[0], history[1], normal_depth, prev_normal_depth, hit, prev_hit
+        const void* in[8] = {b->color[0], b->color[1], b->history[0], b->history[1],
+                             b->normal_depth, b->prev_normal_depth, b->hit, b->prev_hit};
+        void* staged[8] = {};
+        for (int k = 0; k < 8; ++k) {
+            if (!in[k]) continue;  // plane 1 of a one-plane call
+            const size_t n = k < 6 ? bytes : hit_bytes;
+            if ((st = reserve(c, c->d_rep[k], n, "hipMalloc(reproject staging)")) != RT_OK) return st;
+            staged[k] = c->d_rep[k].as<void>();
+            const hipError_t e = hipMemcpyAsync(staged[k], in[k], n, hipMemcpyHostToDevice, stream);
+            if (e != hipSuccess) return hip_fail(c, RT_ERR_LAUNCH, "hipMemcpyAsync(reproject inputs)", e);
+        }
+        for (int k = 0; k < 2; ++k) {
+            A.color[k] = static_cast<const float*>(staged[k]);
+            A.history[k] = static_cast<const float*>(staged[2 + k]);
+            A.out[k] = static_cast<float*>(staged[k]);
+        }
+        A.normal_depth = static_cast<const float*>(staged[4]);
+        A.prev_normal_depth = static_cast<const float*>(staged[5]);
+        A.hit = staged[6];
+        A.prev_hit = staged[7];
+    }
+    if ((st = timed_launch(c, stream, "reproject", &c->launch, [&](rt::LaunchInfo* info) {
+             return rt::launch_reproject(A, planes, stream, info);
+         })) != RT_OK)
+        return st;
+    if (!dev)
+        for (uint32_t k = 0; k < planes; ++k)
+            if ((st = copy_down(c, b->out[k], A.out[k], bytes, stream, "hipMemcpyAsync(reproject out)")) != RT_OK)
+                return st;
+    return finish(c, stream, sync, "reproject execution");
+}
+
 // rt_plan_samples / rt_plan_samples_async: the planner's two kernels
 // (rt_adaptive.hip) on a tile of `rows` rows of the camera's width.  Host
 // images and counts go through the context's staging buffers on its own
@@ -1448,6 +1499,20 @@ int rt_denoise_async(rt_ctx* c, const rt_denoise_params* p, const rt_denoise_buf
     if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
     DeviceGuard g(c->device);
     return denoise_impl(c, p, b_dev, true, (hipStream_t)hip_stream, false);
+}
+
+int rt_reproject(rt_ctx* c, const rt_reproject_params* p, const CameraGPU* prev_camera,
+                 const rt_reproject_buffers* b) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return reproject_impl(c, p, prev_camera, b, p && (p->flags & RT_OUT_DEVICE), c->stream, true);
+}
+
+int rt_reproject_async(rt_ctx* c, const rt_reproject_params* p, const CameraGPU* prev_camera,
+                       const rt_reproject_buffers* b_dev, void* hip_stream) {
+    if (!c) return fail(nullptr, RT_ERR_INVALID_ARG, "ctx is null");
+    DeviceGuard g(c->device);
+    return reproject_impl(c, p, prev_camera, b_dev, true, (hipStream_t)hip_stream, false);
 }
 
 int rt_render_counts(rt_ctx* c, const rt_render_params* p, const uint32_t* counts, void* out, uint32_t* totals) {

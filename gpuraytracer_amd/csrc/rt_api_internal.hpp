@@ -10,6 +10,7 @@
 #include "../../include/rtpt.h"
 #include "rt_kernel.hpp"
 #include "rt_plan.hpp"
+#include "rt_reproject.hpp"
 #include "rt_scene.hpp"
 
 namespace rtapi {
@@ -141,6 +142,18 @@ inline const char* plan_params_error(const rt_plan_params* p, uint32_t flags_ok)
         return "luminance_floor must be > 0 with RT_PLAN_RELATIVE";
     return nullptr;
 }
+
+// rt_reproject, rt_reproject_async and rt_reproject_host (rt_reproject_host.cpp):
+// the checks they share.  reproject_check: empty when params and buffers are
+// fine (*planes: 1 or 2), else what is wrong, naming the field; `flags_ok`: the
+// flag bits the entry point accepts.  reproject_args: the kernel's arguments
+// from checked params and buffers (every pointer as given) and the two
+// cameras; `prev` null means the camera did not move.  False with *why for a
+// prev that compile_camera rejects or of another resolution.
+std::string reproject_check(const rt_reproject_params* p, const rt_reproject_buffers* b, uint32_t flags_ok,
+                            uint32_t* planes);
+bool reproject_args(const rt_reproject_params* p, const rt_reproject_buffers* b, const rt::CamConst& cam,
+                    const CameraGPU* prev, rt::ReprojectArgs* A, std::string* why);
 
 // halton(i, d) of the SwiftPM kernel (Sources/gpuRaytracer/shaders.metal:32-47),
 // the same loop as RTrace/sampling.metal:107-122.

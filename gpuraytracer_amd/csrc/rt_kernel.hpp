@@ -511,6 +511,12 @@ struct DenoiseParams {
 // prepare, variance pre-filter, `iterations` a-trous launches; *info: the last.
 hipError_t launch_denoise(const DenoiseParams& P, hipStream_t stream, LaunchInfo* info);
 
+// ---- temporal reprojection (rt_reproject.hip; include/rtpt.h rt_reproject) --
+// One launch of reproject_kernel<planes> (planes 1 or 2) over whole frames; the
+// arguments and the per-pixel arithmetic are rt_reproject.hpp's.
+struct ReprojectArgs;
+hipError_t launch_reproject(const ReprojectArgs& A, uint32_t planes, hipStream_t stream, LaunchInfo* info);
+
 // ---- sample planner (rt_adaptive.hip; include/rtpt.h rt_plan_samples) -------
 constexpr uint32_t kPlanTile = 16;  // pixels on a side of a workgroup's tile
 // rt_plan_stats, and the planner's accumulators on the device

@@ -1226,23 +1226,10 @@ uint64_t light_mask(const CompiledScene& s) {
     return m;
 }
 
-static bool finite3(const rt_float3& v) {
-    return isfinite(v.x) && isfinite(v.y) && isfinite(v.z);
-}
-
 bool compile_scene(const CameraGPU& cam, const MaterialGPU* mats, const rt_float3* verts,
                    uint32_t n_tri, const SquareLightGPU& light, const SphereGPU* spheres,
                    uint32_t n_sph, CompiledScene* out, const char** err, const BuildOptions& opt) {
-    if (cam.resolution.x <= 0 || cam.resolution.y <= 0) {
-        *err = "camera resolution must be positive";
-        return false;
-    }
-    if (cam.resolution.x / cam.resolution.y == 0) {
-        // aspectRatio = float(res.x / res.y) (sampling.metal:132) would be 0 and
-        // halfHeight infinite: every ray NaN.  Reject instead of rendering NaNs.
-        *err = "camera resolution.x < resolution.y gives aspectRatio 0 (integer division)";
-        return false;
-    }
+    if (!compile_camera(cam, &out->cam, err)) return false;  // rt_camera.cpp
     if (n_tri && (!mats || !verts)) {
         *err = "materials/vertices must be non-null when n_triangles > 0";
         return false;
@@ -1251,45 +1238,6 @@ bool compile_scene(const CameraGPU& cam, const MaterialGPU* mats, const rt_float
         *err = "spheres must be non-null when n_spheres > 0";
         return false;
     }
-    if (!finite3(cam.position) || !finite3(cam.direction) || !finite3(cam.up)) {
-        *err = "camera vectors must be finite";
-        return false;
-    }
-    CamConst& c = out->cam;
-    c.W = cam.resolution.x;
-    c.H = cam.resolution.y;
-    const float aspect = (float)(cam.resolution.x / cam.resolution.y);  // :132
-    c.halfW = tanf(cam.horizontalFov / 2.0f);                            // :133
-    c.halfH = c.halfW / aspect;                                          // :134
-    const f3 w = -normalize(from_abi(cam.direction));                    // :137
-    const f3 u = normalize(cross(from_abi(cam.up), w));                  // :138
-    const f3 v = normalize(cross(w, u));                                 // :139
-    // The same rule as for the portrait frame: a camera whose derived constants
-    // are not all finite makes every camera ray NaN.  Reject instead of rendering NaNs.
-    if (!isfinite(c.halfW) || !isfinite(c.halfH)) {
-        *err = "camera horizontalFov: tan(horizontalFov / 2) is not finite";
-        return false;
-    }
-    const auto unit = [](const f3& a) { return dot(a, a) > 0.5f && isfinite(dot(a, a)); };  // false for NaN
-    if (!unit(w)) {
-        *err = "camera direction: normalize(direction) is not a unit vector (zero length, or its square overflows)";
-        return false;
-    }
-    // cross(up, w) of an up along an oblique direction is rounding noise of w, which
-    // normalizes to some finite roll: the inputs' own cross product tells (in double
-    // a product of two floats is exact and cannot underflow)
-    const double ux = cam.up.x, uy = cam.up.y, uz = cam.up.z;
-    const double dx = cam.direction.x, dy = cam.direction.y, dz = cam.direction.z;
-    const bool parallel = uy * dz == uz * dy && uz * dx == ux * dz && ux * dy == uy * dx;
-    if (!unit(u) || !unit(v) || parallel) {
-        *err = "camera up: cross(up, -direction) does not normalize (up is zero, or parallel to direction)";
-        return false;
-    }
-    const f3 p = from_abi(cam.position);
-    c.pos[0] = p.x; c.pos[1] = p.y; c.pos[2] = p.z;
-    c.u[0] = u.x; c.u[1] = u.y; c.u[2] = u.z;
-    c.v[0] = v.x; c.v[1] = v.y; c.v[2] = v.z;
-    c.w[0] = w.x; c.w[1] = w.y; c.w[2] = w.z;
 
     out->light.center[0] = light.center.x;
     out->light.center[1] = light.center.y;

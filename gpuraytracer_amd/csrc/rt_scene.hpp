@@ -169,6 +169,12 @@ struct BuildOptions {
     uint32_t sphere_leaf_max = 1;  // spheres per leaf (measured best for config 4)
 };
 
+// The camera part of the scene compile (rt_camera.cpp): validates `cam` and
+// makes its constants with the contract ops and the host libm tanf.  False
+// with *err set for a camera that would make every ray NaN.  THE maker of a
+// CamConst: compile_scene, rt_reproject and rt_reproject_host all call it.
+bool compile_camera(const CameraGPU& cam, CamConst* out, const char** err);
+
 // Validates and precomputes; returns false with *err set on bad input.
 bool compile_scene(const CameraGPU& cam, const MaterialGPU* mats, const rt_float3* verts,
                    uint32_t n_tri, const SquareLightGPU& light, const SphereGPU* spheres,

@@ -21,7 +21,7 @@ import numpy as np
 from ._native import (MATH_FNS, RT_MATH_DEVICE, RT_MATH_HOST, RT_MATH_VALUES_MAX, LAYOUTS, RT_AOV_CENTER, RT_COMM_ID_BYTES, RT_KEEP_SUM, RT_OK, RT_OUT_DEVICE, RT_OUT_FP16,
                       RT_OUT_NONE, RT_OUT_RGBA8, RT_RAYS_ANY, RT_RAYS_EXACT, RT_UPDATE_REBUILD, TRI_BUILDS, WALKS,
                       AovBuffers, AovParams, BuildStats, CameraGPU, CreateOptions, DenoiseBuffers, DenoiseParams, LaunchInfo, MaterialGPU, MisParamsC, RayDomainInfo,
-                      PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, RenderParamsC,
+                      PathParamsC, PlanParams, PlanStats, RT_PLAN_RELATIVE, RenderParamsC, ReprojectBuffers, ReprojectParams,
                       RtError, SceneDesc, SceneInfo, SphereGPU, SquareLightGPU, TileLayout, TriBvhDump, UpdateStats, WaveMask, float3,
                       lib)
 
@@ -185,6 +185,74 @@ def plan_samples_host(first, all, budget: int, count_min: int = 0, count_max: in
                                     a.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p),
                                     ctypes.byref(s)))
     return (counts, s.as_dict()) if return_stats else counts
+
+
+def _reproject_params(max_history, normal_cos_min, plane_rel, weight_min) -> ReprojectParams:
+    p = ReprojectParams()
+    lib.rt_reproject_params_default(ctypes.byref(p))
+    p.max_history, p.normal_cos_min, p.plane_rel, p.weight_min = max_history, normal_cos_min, plane_rel, weight_min
+    return p
+
+
+def _planes(x, name):
+    """One frame or a sequence of one or two frames -> list."""
+    planes = list(x) if isinstance(x, (list, tuple)) else [x]
+    if len(planes) not in (1, 2):
+        raise ValueError(f"{name}: one or two planes")
+    return planes
+
+
+def _reproject_host_buffers(shape, color, history, hit, normal_depth, prev_hit, prev_normal_depth, out):
+    """rt_reproject_buffers over host arrays: (buffers, arrays to keep alive, outs)."""
+    color, history = _planes(color, "color"), _planes(history, "history")
+    if len(history) != len(color):
+        raise ValueError("color and history must have the same number of planes")
+    outs = [np.empty(shape, np.float32) for _ in color] if out is None else _planes(out, "out")
+    if len(outs) != len(color):
+        raise ValueError("out must have as many planes as color")
+    b, keep = ReprojectBuffers(), []
+
+    def frame(a, name):
+        if not isinstance(a, np.ndarray) or a.shape != shape:
+            raise ValueError(f"{name} must be a {shape} float32 array")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep.append(a)
+        return a.ctypes.data
+
+    def hits(a, name):
+        if not isinstance(a, np.ndarray) or a.nbytes != 8 * shape[0] * shape[1] or a.shape[:2] != shape[:2]:
+            raise ValueError(f"{name} must hold one 8-byte (t, id) record per pixel of the {shape[:2]} frame")
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data
+
+    for k in range(len(color)):
+        b.color[k] = frame(color[k], f"color[{k}]")
+        b.history[k] = frame(history[k], f"history[{k}]")
+        o = outs[k]
+        if not isinstance(o, np.ndarray) or o.dtype != np.float32 or o.shape != shape or not o.flags.c_contiguous:
+            raise ValueError(f"out[{k}] must be a contiguous {shape} float32 array")
+        b.out[k] = o.ctypes.data
+    b.hit, b.prev_hit = hits(hit, "hit"), hits(prev_hit, "prev_hit")
+    b.normal_depth = frame(normal_depth, "normal_depth")
+    b.prev_normal_depth = frame(prev_normal_depth, "prev_normal_depth")
+    return b, keep, outs
+
+
+def reproject_host(camera: CameraGPU, prev_camera, color, history, hit, normal_depth, prev_hit, prev_normal_depth,
+                   max_history: int = 32, normal_cos_min: float = 0.9, plane_rel: float = 2.0 ** -7,
+                   weight_min: float = 0.0625, out=None) -> list:
+    """rt_reproject_host: ``Renderer.reproject`` in plain C++ on the host (no
+    device, no context), bit for bit the same planes.  ``camera`` is the
+    current CameraGPU, ``prev_camera`` the previous one (None: it did not
+    move); the buffers are numpy arrays as for the host path of
+    :meth:`Renderer.reproject`.  Returns the list of output planes."""
+    shape = (camera.resolution.y, camera.resolution.x, 4)
+    b, keep, outs = _reproject_host_buffers(shape, color, history, hit, normal_depth, prev_hit, prev_normal_depth, out)
+    p = _reproject_params(max_history, normal_cos_min, plane_rel, weight_min)
+    _check(lib.rt_reproject_host(ctypes.byref(camera), ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                 ctypes.byref(p), ctypes.byref(b)))
+    return outs
 
 
 def _tri_bvh_dump(call, n: int, nodes_cap: int) -> dict:
@@ -860,6 +928,116 @@ class Renderer:
         if hasattr(s, "synchronize"):
             s.synchronize()
         return (img, inputs) if return_inputs else img
+
+    def reproject(self, color, history, hit, normal_depth, prev_hit, prev_normal_depth, prev_camera=None,
+                  max_history: int = 32, normal_cos_min: float = 0.9, plane_rel: float = 2.0 ** -7,
+                  weight_min: float = 0.0625, out=None, stream=None) -> list:
+        """Temporal reprojection (rt_reproject): this frame's
+        ``color`` plane(s) blended with the previous frame's ``history``
+        plane(s), gathered where this frame's surface points were seen from
+        ``prev_camera`` (a CameraGPU; None: the camera did not move).  The
+        current camera is the context's.  ``color`` / ``history`` / ``out``: one
+        (H, W, 4) float32 frame or a sequence of one or two; ``hit`` /
+        ``normal_depth``: this frame's ``render_aov(center=True)`` buffers,
+        ``prev_hit`` / ``prev_normal_depth``: the previous frame's.  Returns the
+        list of output planes (rgb mean, alpha = history length); they are the
+        next call's ``history``.
+
+        numpy arrays take the host path and block.  Contiguous torch tensors on
+        the context's device (hits as (H, W, 2) int32) take the device path,
+        enqueued on ``stream`` without a host sync (default: torch's current
+        stream, then waited for).  ``out[k]`` may be ``color[k]``; it must not
+        overlap a history plane."""
+        p = _reproject_params(max_history, normal_cos_min, plane_rel, weight_min)
+        H, W = self.scene.height, self.scene.width
+        shape = (H, W, 4)
+        cam = ctypes.byref(prev_camera) if prev_camera is not None else None
+        first = _planes(color, "color")[0]
+        if isinstance(first, np.ndarray):
+            b, keep, outs = _reproject_host_buffers(shape, color, history, hit, normal_depth, prev_hit,
+                                                    prev_normal_depth, out)
+            _check(lib.rt_reproject(self._ctx, ctypes.byref(p), cam, ctypes.byref(b)), self._ctx)
+            return outs
+        import torch  # plumbing only: device memory and the caller's stream
+        color, history = _planes(color, "color"), _planes(history, "history")
+        outs = [torch.empty(shape, dtype=torch.float32, device=first.device) for _ in color] if out is None \
+            else _planes(out, "out")
+        if len(history) != len(color) or len(outs) != len(color):
+            raise ValueError("color, history and out must have the same number of planes")
+        b = ReprojectBuffers()
+
+        def ptr(t, name, shp=shape, dt=torch.float32):
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous()
+                    or not t.is_cuda or t.device.index != self.device):
+                raise ValueError(f"{name} must be a contiguous {shp} {dt} tensor on the context's device")
+            return t.data_ptr()
+
+        for k in range(len(color)):
+            b.color[k] = ptr(color[k], f"color[{k}]")
+            b.history[k] = ptr(history[k], f"history[{k}]")
+            b.out[k] = ptr(outs[k], f"out[{k}]")
+        b.hit = ptr(hit, "hit", (H, W, 2), torch.int32)
+        b.prev_hit = ptr(prev_hit, "prev_hit", (H, W, 2), torch.int32)
+        b.normal_depth = ptr(normal_depth, "normal_depth")
+        b.prev_normal_depth = ptr(prev_normal_depth, "prev_normal_depth")
+        p.flags = RT_OUT_DEVICE
+        cur, handle = self._stream_handle(stream)
+        _check(lib.rt_reproject_async(self._ctx, ctypes.byref(p), cam, ctypes.byref(b), ctypes.c_void_p(handle)),
+               self._ctx)
+        if cur is not None:
+            cur.synchronize()
+        return outs
+
+    def render_temporal(self, params: RenderParams | None = None, state=None, denoise: bool = True, stream=None,
+                        reproject_args: dict | None = None, **filter_args):
+        """One frame of a temporally accumulated sequence: returns
+        ``(image, state)``; pass ``state`` to the next call (after
+        :meth:`update_scene` when the camera moved), ``state=None`` starts a
+        sequence.  Frame ``f`` renders ``spp / 2 + spp / 2`` samples at
+        ``sample_base + f * spp`` (so frames draw different samples) and the
+        centre feature buffers, reprojects both planes against ``state`` (the
+        previous camera, hit, normal_depth and both outputs;
+        ``reproject_args`` pass to :meth:`reproject`) and, with ``denoise``,
+        filters the accumulated planes with the jittered feature buffers of
+        the frame's samples as :meth:`render_denoised` does (``filter_args``
+        pass to :meth:`denoise`); without it ``image`` is the list of the two
+        accumulated planes.  Everything runs on device tensors and one stream (default:
+        torch's current stream), then waited for.  The image's alpha is plane
+        0's history length (1: no history reused).  Needs an even ``spp`` >= 2 and whole float32
+        frames."""
+        p = params or RenderParams()
+        H, W = self.scene.height, self.scene.width
+        if p.spp < 2 or p.spp % 2:
+            raise ValueError("render_temporal needs an even spp >= 2 (two halves)")
+        if p.row_start != 0 or p.row_step not in (0, 1) or p.row_count not in (0, H):
+            raise ValueError("render_temporal needs whole frames (no row partition)")
+        if p.accumulate or p.keep_sum or p.fp16 or p.rgba8:
+            raise ValueError("render_temporal renders plain float32 frames (no accumulate, keep_sum, fp16, rgba8)")
+        import torch  # plumbing only: device memory and the caller's stream
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        frame = 0 if state is None else state["frame"] + 1
+        half, base = p.spp // 2, p.sample_base + frame * p.spp
+        new = lambda: torch.empty((H, W, 4), dtype=torch.float32, device=dev)  # noqa: E731
+        planes = [new(), new()]
+        self.render(RenderParams(spp=half, bounces=p.bounces, sample_base=base), out=planes[0], stream=s)
+        self.render(RenderParams(spp=half, bounces=p.bounces, sample_base=base + half), out=planes[1], stream=s)
+        centre = {"normal_depth": new(), "first_hit": torch.empty((H, W, 2), dtype=torch.int32, device=dev)}
+        self.render_aov(center=True, out=centre, stream=s)
+        if state is not None:
+            self.reproject(planes, state["out"], centre["first_hit"], centre["normal_depth"], state["hit"],
+                           state["normal_depth"], prev_camera=state["camera"], out=planes, stream=s,
+                           **(reproject_args or {}))
+        img = planes
+        if denoise:
+            aov = {"albedo": new(), "normal_depth": new()}
+            self.render_aov(spp=p.spp, sample_base=base, out=aov, stream=s)
+            img = self.denoise(planes[0], planes[1], aov["albedo"], aov["normal_depth"], stream=s, **filter_args)
+        if hasattr(s, "synchronize"):
+            s.synchronize()
+        state = {"frame": frame, "camera": CameraGPU.from_buffer_copy(self.scene.camera), "out": planes,
+                 "hit": centre["first_hit"], "normal_depth": centre["normal_depth"]}
+        return img, state
 
     def _stream_handle(self, stream):
         """(torch stream to wait for or None, raw hipStream_t) for a device call."""

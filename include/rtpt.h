@@ -440,6 +440,92 @@ int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_bu
 int rt_denoise_async(rt_ctx* ctx, const rt_denoise_params* params, const rt_denoise_buffers* buffers_dev,
                      void* hip_stream);
 
+/* ---- temporal accumulation under a moving camera -----------------------------
+ * rt_reproject carries the accumulated colour of the previous frame over to
+ * this frame's pixels (Schied et al. 2017, the temporal half): the world point
+ * a pixel's centre ray hit is projected into the previous camera, the previous
+ * outputs are gathered there bilinearly from the taps that show the same
+ * primitive with a like normal near the pixel's tangent plane, and this
+ * frame's colour is blended in with weight 1 / n, n the gathered history
+ * length + 1 capped at max_history.  out.rgb is the new mean and out.a = n; a
+ * pixel without usable history (a miss, a point behind or outside the previous
+ * frame, the other side of a surface, too little tap weight) gives
+ * (color.rgb, 1).  So the outputs of one call are the histories of the next,
+ * and the first frame's rt_render output (a = 1) is a valid history.  Two
+ * colour planes (the two half renders rt_denoise wants) share one set of tap
+ * tests.  The arithmetic is fixed operation by operation:
+ * the output is a function of the buffers, the two cameras and the parameters
+ * alone, bit for bit, and it is defined for any bytes in any buffer: no read
+ * leaves the frame.  When every history alpha is >= 1, reuse shows as
+ * out.a > 1.
+ *
+ * Per frame: rt_render the colour plane(s), rt_render_aov with RT_AOV_CENTER
+ * into first_hit and normal_depth, and keep both and the camera for the next
+ * frame.  The current camera is the context's (after rt_update_scene: the new
+ * pose); prev_camera is a host pointer, NULL when the camera did not move, and
+ * must have the context's resolution.  Geometry that moved between the frames
+ * is not compensated: only the tap tests reject its history.
+ *
+ * All frames are whole frames of the camera resolution (no row partition: a
+ * filter needs its neighbours).  No seeds are needed.  The context owns the
+ * staging of host buffers, grown on first use and freed by rt_destroy; calls
+ * on one context must be ordered.
+ *
+ * These entry points were added without a change of RTPT_ABI_VERSION (nothing
+ * else changed): a caller that may meet an older library detects the feature
+ * by the presence of the symbol rt_reproject (dlsym). */
+typedef struct rt_reproject_params {
+    uint32_t max_history;     /* 1 .. 65536: cap of the history length n (blend weight >= 1/max_history) */
+    float    normal_cos_min;  /* -1 .. 1: a tap needs dot(N, N_tap) >= this                               */
+    float    plane_rel;       /* >= 0: a tap's world point may lie plane_rel * r off the pixel's tangent
+                                 plane, r = distance of the point from the previous camera                */
+    float    weight_min;      /* (0, 1]: least sum of valid bilinear weights for reuse                    */
+    uint32_t flags;           /* RT_OUT_DEVICE                                                            */
+    uint32_t reserved[3];     /* must be 0                                                                */
+} rt_reproject_params; /* 32 B */
+
+typedef struct rt_reproject_buffers {
+    const float*      color[2];          /* H*W rgba32F: this frame's renders; [1] may be NULL (one plane)  */
+    const float*      history[2];        /* H*W rgba32F: previous out[k] (rgb mean, a = history length);
+                                            the first frame's rt_render output (a = 1) is a valid history   */
+    const rt_ray_hit* hit;               /* this frame, rt_render_aov with RT_AOV_CENTER: first_hit         */
+    const float*      normal_depth;      /* this frame, the same call: normal_depth                         */
+    const rt_ray_hit* prev_hit;          /* the previous frame's two buffers                                */
+    const float*      prev_normal_depth;
+    float*            out[2];            /* H*W rgba32F; out[k] may be color[k]; must not overlap a history */
+} rt_reproject_buffers; /* 80 B */
+
+/* max_history 32, normal_cos_min 0.9f, plane_rel 0x1p-7f, weight_min 0.0625f,
+ * flags 0, reserved {0, 0, 0}. */
+void rt_reproject_params_default(rt_reproject_params* params);
+
+/* Reproject and block until done.  The buffers are host memory (the context's
+ * staging buffers carry them), or all device memory with RT_OUT_DEVICE.
+ * color[1], history[1] and out[1] are all NULL (one plane) or all non-NULL.
+ * RT_ERR_INVALID_ARG, with an rt_last_error message that names the field: a
+ * NULL context, params, buffers or required pointer, a mixed plane 1, a
+ * parameter outside its range (NaN included), an unknown flag bit, nonzero
+ * reserved, a prev_camera that rt_create would reject or of another
+ * resolution.  RT_ERR_STATE: a context left broken by a failed
+ * rt_update_scene.  rt_last_launch then names "rt::reproject_kernel<1>" or
+ * "<2>" (the planes) with its grid, block and LDS bytes, and rt_last_kernel_ms
+ * gives the device time. */
+int rt_reproject(rt_ctx* ctx, const rt_reproject_params* params, const CameraGPU* prev_camera,
+                 const rt_reproject_buffers* buffers);
+
+/* Asynchronous variant: every buffer is device memory (prev_camera stays a
+ * host pointer, read before the call returns), the kernel is enqueued on
+ * `hip_stream` (a hipStream_t, NULL = the null stream).  No host sync. */
+int rt_reproject_async(rt_ctx* ctx, const rt_reproject_params* params, const CameraGPU* prev_camera,
+                       const rt_reproject_buffers* buffers_dev, void* hip_stream);
+
+/* The same function on the host: no device, no context; `camera` is the
+ * current camera (required), every buffer is host memory and no flag is
+ * accepted.  Bit for bit what rt_reproject computes (one per-pixel function
+ * compiled for both).  Errors go to rt_last_error(NULL). */
+int rt_reproject_host(const CameraGPU* camera, const CameraGPU* prev_camera, const rt_reproject_params* params,
+                      const rt_reproject_buffers* buffers);
+
 /* ---- adaptive sampling: per-pixel sample counts and a sample planner --------
  * rt_render_counts is rt_render with one sample count per pixel; rt_plan_samples
  * makes such counts from a pilot render.  These entry points

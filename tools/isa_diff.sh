@@ -33,7 +33,7 @@ CC=$(make -s -C "$R" --eval 'isa-cc: ; @echo $(HIPCC) $(HIPFLAGS)' isa-cc)
 OLD="$T/old"
 [ -z "${ISA_OLD_DIR:-}" ] ||
     OLD="$(mkdir -p "$ISA_OLD_DIR" && cd "$ISA_OLD_DIR" && pwd)/$(git -C "$T/rev" rev-parse HEAD)-$(echo "$CC" | sha256sum | cut -c1-12)"
-FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_refit rt_aov rt_denoise rt_adaptive rt_mathcheck"
+FILES="rt_kernel rt_mis rt_rays rt_lbvh rt_gsah rt_refit rt_aov rt_denoise rt_reproject rt_adaptive rt_mathcheck"
 mkdir -p "$T/new" "$OLD"
 export CC T
 for f in $FILES; do
