@@ -247,8 +247,16 @@ static bool same_bits(const float* a, const float* b, int n) {
 }
 
 // Conservative culling margin: far above the fp32 rounding of the triangle
-// test at the scene's scale (~1e-6 relative), far below the 1e-3 surface
-// offset of raytrace.metal:67.
+// test at the scene's scale (~1e-6 relative).  Below an
+// extent of 25 it is also below the 1e-3 surface offset of raytrace.metal:67,
+// so a ray that leaves a surface starts outside that surface's padded box; from
+// 25 on (4e-5 * 25 = 1e-3) it is not: 0.01 for a room of 100x the Cornell
+// size, 0.036 with its camera at 900.  The offset is a constant of the
+// reference and does not scale with the scene; the rounding the margin covers
+// does.  A margin above the offset costs culling, never a result: padding only
+// adds candidates, and the exact test decides each of them.  Extents of 92,
+// 250, 257.5 and 902.5 render bit for bit (tests/test_gpu_transforms.py,
+// DESIGN.md §4).
 static float culling_margin(const rt_float3* verts, uint32_t n_tri, const SphereGPU* sph = nullptr,
                             uint32_t n_sph = 0, float rel = 4e-5f) {
     float ext = 2.5f;

@@ -7,9 +7,11 @@
 // the kernel's float order) must have no accepted hit (t in (0.001, tmax)) on
 // any triangle of the container -- half of them with an end pulled to within a
 // few ulps of a shrunk plane, where the rounding matters.
-//   cluster_check <mis 0|1> <seed> [widen]   (exit 0 and "ok" on success; a
-//   positive `widen` grows the stored box by that much, a negative control that
-//   must fail)
+//   cluster_check <mis 0|1> <seed> [widen] [scene file]   (exit 0 and "ok" on
+//   success; a positive `widen` grows the stored box by that much, a negative
+//   control that must fail; with a scene file -- the format of
+//   closest_order_host.hpp -- that scene takes the place of the Cornell room,
+//   and the segment and container counts are printed after "ok")
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -19,8 +21,7 @@
 #include <random>
 #include <vector>
 
-#include "rt_scene.hpp"
-#include "../../oracle/pt_oracle.h"
+#include "closest_order_host.hpp"
 
 #define CHECK(c, ...)                                   \
     do {                                                \
@@ -35,19 +36,25 @@ int main(int argc, char** argv) {
     const bool mis = argc > 1 && atoi(argv[1]) != 0;
     const unsigned seed = argc > 2 ? (unsigned)atoi(argv[2]) : 1u;
     const float widen = argc > 3 ? (float)atof(argv[3]) : 0.0f;
-    CameraGPU cam;
-    MaterialGPU mats[64];
-    rt_float3 verts[192];
-    SquareLightGPU light;
-    uint32_t nt = 0;
-    CHECK((mis ? pto_cornell_box_mis : pto_cornell_box)(64, 48, &cam, mats, verts, &light, &nt) == 0,
-          "scene");
-    rt::CompiledScene cs;
     const char* err = nullptr;
-    CHECK(rt::compile_scene(cam, mats, verts, nt, light, nullptr, 0, &cs, &err), "compile: %s", err);
+    clo::HostScene hs;
+    if (argc > 4) {
+        CHECK(clo::load_scene(argv[4], &hs, &err), "scene file: %s", err ? err : "?");
+    } else {
+        hs.mats.resize(64);
+        hs.verts.resize(192);
+        CHECK((mis ? pto_cornell_box_mis : pto_cornell_box)(64, 48, &hs.cam, hs.mats.data(), hs.verts.data(),
+                                                            &hs.light, &hs.nt) == 0,
+              "scene");
+        CHECK(rt::compile_scene(hs.cam, hs.mats.data(), hs.verts.data(), hs.nt, hs.light, nullptr, 0, &hs.cs, &err),
+              "compile: %s", err);
+    }
+    const rt::CompiledScene& cs = hs.cs;
+    const std::vector<rt_float3>& verts = hs.verts;
     const size_t rec = 28;
     const size_t nc = cs.clusters.size() / rec;
     int containers = 0;
+    long tested_all = 0;
     std::mt19937 g(seed);
     std::uniform_real_distribution<float> U(0.0f, 1.0f);
     for (size_t c = 0; c < nc; ++c) {
@@ -117,8 +124,9 @@ int main(int argc, char** argv) {
             }
         }
         CHECK(tested > 1000, "too few segments passed the container test (%ld)", tested);
+        tested_all += tested;
     }
     CHECK(containers == 1, "expected one container (the room), got %d", containers);
-    printf("ok\n");
+    printf("ok containers=%d segments=%ld\n", containers, tested_all);
     return 0;
 }

@@ -200,12 +200,13 @@ def d_spheres(scene, count=16):
     return np.concatenate(rows)
 
 
-def set_d(scene, B, ref_b, pairs=True):
-    """The whole of set D for a scene; ``ref_b`` is B's closest reference."""
+def set_d(scene, B, ref_b, pairs=True, origin=INTERIOR):
+    """The whole of set D for a scene; ``ref_b`` is B's closest reference,
+    ``origin`` the origin of the corner and edge rays."""
     t, ids = ref_b
     parts = [d_tmax_at_hit(B, t, ids), d_tmin_at_hit(B, t, ids)]
     if pairs:
-        parts.append(d_pair_corners(scene))
+        parts.append(d_pair_corners(scene, origin))
     parts += [d_in_plane(scene), d_on_face(scene), d_axis_zero_signs(), d_spheres(scene)]
     return np.concatenate(parts)
 

@@ -27,6 +27,13 @@ def check_table(scene, params, lanes, shape):
     with Renderer(scene, options=Options(lanes=lanes)) as r:
         rec, fills = r.wave_masks(params, lanes)
     assert fills == 1 and rec.size, (fills, rec.shape)
+    return check_records(scene, params, rec, shape)
+
+
+def check_records(scene, params, rec, shape):
+    """``rec``, the table some context of ``scene`` gave for ``params``, equals the
+    host's on every wave that holds a pixel (as check_table returns)."""
+    assert rec.size, rec.shape
     q0 = rec[0, 0]
     assert (q0["x1"] - q0["x0"] + 1, (q0["y1"] - q0["y0"]) // params.row_step + 1) == shape, q0
     last_row = params.row_start + (params.rows(scene.height) - 1) * params.row_step
